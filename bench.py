@@ -23,6 +23,12 @@ Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes per laun
 of the plan's kernels measured with HIP events on the launch stream inside the library.
 `--dry-run` (CPU, gloo, no kernels) exercises only the launch / collective / report plumbing and says
 so in the line (`"dry_run": true`, value 0): it is what the CPU test of the N > 1 path runs.
+
+A plain run sets up, warms up, times --steps steps and prints the line: `value`, `ms_per_step` and the roofline of
+those steps.  Everything else it can measure -- the CPU baselines, the other BASELINE configs, the library-default
+options, the HBM traffic counted by rocprofv3 child runs, the strong-scaling regime of an N > 1 weak run -- is
+measured only with `--full` (`--extras` asks for its own figures).  `--dump-outputs DIR` writes the result of the last timed step as DIR/<column>.npy
+(see dump_outputs): the inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -566,18 +572,24 @@ def parse_args(argv=None):
                          "shard scan -> ONE all-to-all of slot slices -> element-wise fold + extraction, no merge plan; all_gather = every "
                          "packed partial table to every rank, every rank merges all of them; key_range = a partial row goes to the owner of "
                          "its key (one all-to-all), every rank merges 1/N of the groups")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baselines, the other BASELINE configs, the library-default "
+                         "options, HBM traffic from rocprofv3 child runs, both scaling regimes of an N > 1 weak run (the --no-* options below "
+                         "take parts of it out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the result of the last timed step to DIR/<column>.npy (float64; float32 for FLOAT columns)")
     ap.add_argument("--cpu-sample-rows", type=int, default=0, help="0 = 16 M (wide) / 4 M (group)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not count HBM traffic with rocprofv3 --pmc child runs (roofline.traffic is then read from the committed pass)")
+                    help="--full: do not count HBM traffic with rocprofv3 --pmc child runs (roofline.traffic is then read from the committed pass)")
     ap.add_argument("--no-specialize", action="store_true",
                     help="run the interpreting pipeline kernel instead of the one specialised for the plan by runtime compilation")
     ap.add_argument("--extras", action="store_true", help="also report 1 % / 99 % selectivity and the PCIe-inclusive rate (N = 1)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="N = 1, --query wide: do not measure the other BASELINE configs (group3, group, sort, filter_mat) after the headline's timed region")
+                    help="--full, N = 1, --query wide: do not measure the other BASELINE configs (group3, group, sort, filter_mat) after the headline's timed region")
     ap.add_argument("--config-steps", type=int, default=30, help="timed steps of each of those configs")
     ap.add_argument("--no-regimes", action="store_true",
-                    help="distributed runs: report only the regime --scaling names, not both (weak: --rows per GPU; strong: --rows in total)")
+                    help="--full, distributed runs: report only the regime --scaling names, not both (weak: --rows per GPU; strong: --rows in total)")
     ap.add_argument("--tile-rows", type=int, default=0)
     ap.add_argument("--lds-target", type=int, default=0)
     ap.add_argument("--grid-limit", type=int, default=0)
@@ -594,7 +606,10 @@ def parse_args(argv=None):
                     help="take the N > 1 code path (partial run + RCCL exchange + merge / finalize) even with one rank")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU / gloo, no kernels: only the launch, collective and report plumbing (tests)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def metric_name(query):
@@ -645,7 +660,7 @@ def dry_run(args, world, rank):
         assert gathered.view(world, 56)[:, 0].tolist() == list(range(world))
     # the second regime of a weak run (see main): the same loop once more, timed the same way
     regimes = None
-    if dist.is_initialized() and args.scaling == "weak" and not args.no_regimes:
+    if dist.is_initialized() and args.full and args.scaling == "weak" and not args.no_regimes:
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
@@ -716,6 +731,61 @@ def extras(ss, torch, ctx, device, rows, cols, view):
         lib.ssgpu_host_free(ctx.handle, p)
     lib.ssgpu_block_destroy(blk)
     return out
+
+
+# ---- --dump-outputs: what the timed path computed, for output-by-output comparison of two builds ------------------------------
+DUMP_BYTES = 48 << 20      # a result larger than this (at 8 bytes a value) is written as a fixed, seeded sample of its rows
+
+
+def dump_outputs(out_dir, plan, result=None, key_columns=0, torch=None, device=None):
+    """Writes the result of the timed path's last step, one DIR/<column>.npy per result column -- float32 for FLOAT columns,
+    float64 otherwise (an INT64 beyond 2^53 is rounded), NULL as NaN -- and DIR/row_count.npy.  `result` is the host View the
+    path fetched from `plan`, or None when the result stays in HBM (Sort, materialising Filter): then `plan`'s device result is
+    read.  The first `key_columns` columns are group keys: a GroupAggregate's rows come in no defined order, so they are written
+    sorted by those keys.  A result larger than DUMP_BYTES is written as its rows at sorted positions drawn with a fixed seed."""
+    import numpy as np
+    from supersonic_amd import api
+    schema = plan.result_schema
+    attrs = [schema.attribute(i) for i in range(schema.attribute_count())]
+    if result is not None:
+        rows = result.row_count()
+        cols = [(np.asarray(result.column(i).data), result.column(i).is_null) for i in range(len(attrs))]
+    else:
+        dv = plan.result_device_view()
+        rows = dv.row_count()
+        cols = None
+    cap = DUMP_BYTES // (8 * max(len(attrs), 1))
+    pos = None if rows <= cap else np.unique(np.random.default_rng(0).integers(0, rows, cap))
+    if cols is None:                       # gather the sampled rows on the device, copy only them
+        idx = None if pos is None else torch.as_tensor(pos, device=device)
+
+        def read(ptr, typestr):
+            t = torch.as_tensor(_DevPtr(ptr, rows, typestr), device=device)
+            return (t if idx is None else t[idx]).cpu().numpy()
+        cols = []
+        for i, a in enumerate(attrs):
+            if a.type() not in api._NP:
+                raise SystemExit("--dump-outputs: column %s is not numeric" % a.name())
+            dt = np.dtype(api._NP[a.type()])
+            data_ptr, null_ptr = dv._ptrs[i]
+            cols.append((read(data_ptr, dt.str) if rows else np.zeros(0, dt), (read(null_ptr, "|u1") != 0) if rows and null_ptr else None))
+        pos = None                         # already sampled
+    order = None
+    if key_columns and rows:
+        order = np.lexsort([cols[k][0] for k in reversed(range(key_columns))])
+    os.makedirs(out_dir, exist_ok=True)
+    for a, (data, nulls) in zip(attrs, cols):
+        if data.dtype == object:
+            raise SystemExit("--dump-outputs: column %s is not numeric" % a.name())
+        out = data.astype(np.float32 if data.dtype == np.float32 else np.float64)
+        if nulls is not None:
+            out[nulls] = np.nan
+        if order is not None:
+            out = out[order]
+        if pos is not None:
+            out = out[pos]
+        np.save(os.path.join(out_dir, a.name() + ".npy"), out)
+    np.save(os.path.join(out_dir, "row_count.npy"), np.array([rows], dtype=np.float64))
 
 
 def main():
@@ -923,7 +993,7 @@ def main():
     # the first rows / N of its columns -- with the same barrier + max-over-ranks clock.  The single-GPU time of the same
     # plan over all --rows rows, measured on this very box, is reported next to them (the reader divides; no efficiency is claimed here).
     regimes = None
-    if distributed and not args.no_regimes and args.scaling == "weak":
+    if distributed and args.full and not args.no_regimes and args.scaling == "weak":
         def timed(fn, k):
             barrier()
             t0 = time.perf_counter()
@@ -980,6 +1050,9 @@ def main():
         result = None
     else:
         result = (job.result()[0] if job is not None else plan).fetch()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, job.result()[0] if job is not None else plan, result, key_columns=2 if group else 0,
+                     torch=torch, device=device)
     if rank == 0:
         value = total_rows_per_step * args.steps / elapsed
         avg_kernel_s = (sum(kernel_ms) / len(kernel_ms)) / 1e3
@@ -1041,7 +1114,7 @@ def main():
                 line["config"]["dense_layout"] = job.layout
         if regimes is not None:
             line["regimes"] = regimes
-        if world == 1 and not distributed and args.query == "wide" and QUERY_NAME == "wide" and not args.no_configs:
+        if args.full and world == 1 and not distributed and args.query == "wide" and QUERY_NAME == "wide" and not args.no_configs:
             # the other BASELINE configs on the SAME box, after the headline's timed region (its value, ms_per_step and roofline are
             # untouched): config #3 (group3), config #4's per-GPU query (group), config #5 (sort), the materialising Filter
             line["configs"] = {}
@@ -1054,7 +1127,7 @@ def main():
                     line["configs"][q] = dict(line["configs"].get(q) or {}, error="%s: %s" % (type(e).__name__, e))
         if world == 1 and args.extras and args.query == "wide":
             line["extras"] = extras(ss, torch, ctx, device, rows, cols, view)
-        if world == 1 and not distributed and args.query == "wide" and QUERY_NAME == "wide" and not os.environ.get("SSGPU_BENCH_CHILD"):
+        if args.full and world == 1 and not distributed and args.query == "wide" and QUERY_NAME == "wide" and not os.environ.get("SSGPU_BENCH_CHILD"):
             # the same plan under the LIBRARY'S DEFAULT options (a context nobody tuned: specialize = 3 -- the compiled kernel where one
             # exists, here the one the headline compiled --, lazy_feedback = 0 -- every run settled before ssgpu_plan_run returns):
             # what a caller who sets nothing gets, next to the tuned headline (round-5 advice)
@@ -1077,7 +1150,7 @@ def main():
                 del dplan, dctx
             except Exception as e:   # noqa: BLE001
                 line["default_options"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if (world == 1 and not distributed and not args.no_traffic and not os.environ.get("SSGPU_BENCH_CHILD")
+        if (args.full and world == 1 and not distributed and not args.no_traffic and not os.environ.get("SSGPU_BENCH_CHILD")
                 and not any(k.startswith("ROCP") for k in os.environ)):      # (not when this process itself runs under rocprofv3)
             # this command's own counters (the timed region is over; the children are separate processes on the same GPU)
             measured, detail = measure_traffic(QUERY_NAME, rows, alg_bytes)
@@ -1087,7 +1160,7 @@ def main():
                                                            "FETCH_SIZE x 2 for streaming reads (gfx950), counters in KiB", "traffic_kernels": detail})
             else:
                 line["roofline"]["traffic_note"] = "not counted in this run (%s): read from the committed pass" % detail
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(ss, args.query, args.cpu_sample_rows or {"wide": 16_000_000, "filter_mat": 16_000_000}.get(args.query, 4_000_000))
         # RCCL prints its version banner through C stdio (still buffered when stdout is a file):
         # drain it first so that the JSON line is the LAST line of stdout

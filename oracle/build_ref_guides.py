@@ -3,17 +3,18 @@ against this repository's headers and library:
 
     g++ -std=c++14 -I<repo>/include -I<repo>/tests/cpp/minigtest <reference>/test/guide/<name>.cc -lssgpu
 
-Nothing of the reference is copied: the source stays where it lies, the binary goes to tests/cpp/_build/ (git-ignored, like
-every built artefact; it travels to the GPU box with the other built files, where `tests/test_cpp_facade.py` runs it).
+Nothing of the reference is copied: the source stays where it lies, the binary goes to oracle/_ref/ (git-ignored; what
+build() leaves there travels with the tree to the GPU machine, where `tests/test_cpp_facade.py` runs it: its rpath
+points at supersonic_amd/lib relative to the binary, so the checkout may lie anywhere).
 `gtest/gtest.h` resolves to tests/cpp/minigtest -- this repository's own small harness with googletest's macro surface.
-Without a reference checkout (the GPU box) this does nothing."""
+Without a reference checkout (the GPU machine) this does nothing."""
 import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE = os.environ.get("SUPERSONIC_REFERENCE", "/root/reference")
-OUT_DIR = os.path.join(ROOT, "tests", "cpp", "_build")
+OUT_DIR = os.path.join(ROOT, "oracle", "_ref")
 LIBDIR = os.path.join(ROOT, "supersonic_amd", "lib")
 GUIDES = ("primer", "group_sort")
 
@@ -37,13 +38,13 @@ def build(name, force=False):
     if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         tmp = "%s.%d.tmp" % (out, os.getpid())
         subprocess.check_call(["g++", "-std=c++14", "-O1", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "cpp", "minigtest"),
-                               src, "-o", tmp, "-L" + LIBDIR, "-lssgpu", "-Wl,-rpath," + LIBDIR])
+                               src, "-o", tmp, "-L" + LIBDIR, "-lssgpu", "-Wl,-rpath,$ORIGIN/../../supersonic_amd/lib"])
         os.replace(tmp, out)
     return out
 
 
 def expected():
-    """Guide binaries the build container said it built (tests/cpp/_build/EXPECTED, written by mark_expected)."""
+    """Guide binaries the build container said it built (oracle/_ref/EXPECTED, written by mark_expected)."""
     try:
         with open(os.path.join(OUT_DIR, "EXPECTED")) as f:
             return [ln.strip() for ln in f if ln.strip()]

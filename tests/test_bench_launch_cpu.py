@@ -26,7 +26,7 @@ def run_bench(*extra, env_extra=None):
 
 @pytest.mark.parametrize("query,scaling", [("wide", "weak"), ("group", "strong")])
 def test_bench_gpus_2_launches_two_ranks(query, scaling):
-    line = run_bench("--gpus", "2", "--query", query, "--scaling", scaling, "--rows", "1000")
+    line = run_bench("--gpus", "2", "--query", query, "--scaling", scaling, "--rows", "1000", "--full")
     assert line["n_gpus"] == 2 and line["dry_run"] is True and line["scaling"] == scaling
     assert line["steps"] == 5 and line["warmup"] == 2
     assert line["config"]["collectives_per_step"] == 1
@@ -42,3 +42,10 @@ def test_bench_gpus_2_launches_two_ranks(query, scaling):
 def test_bench_default_is_one_gpu():
     line = run_bench()
     assert line["n_gpus"] == 1 and line["higher_is_better"] is True and line["unit"] == "rows/s"
+
+
+def test_bench_plain_run_times_only_its_own_regime():
+    # the second regime of a weak run is measured with --full only
+    line = run_bench("--gpus", "2", "--rows", "1000")
+    assert line["n_gpus"] == 2 and line["steps"] == 5 and line["ms_per_step"] > 0
+    assert "regimes" not in line

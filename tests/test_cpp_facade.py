@@ -2,7 +2,6 @@
 builder API (supersonic/supersonic.h) driven from C++ exactly as its guide tests do."""
 import os
 import subprocess
-import sys
 
 import pytest
 
@@ -72,19 +71,18 @@ def test_guide_style_program_runs(guide_bin):
     _run(guide_bin, "run")
 
 
-# ---- the reference's OWN guide programs, unchanged: /root/reference/test/guide/{primer,group_sort}.cc are compiled where they
-# lie (nothing is copied) against -I<repo>/include and linked with libssgpu; the binaries are built in the build container
-# (also by __graft_entry__.build()) and travel to the GPU box as built artefacts, where they RUN: every TEST of the guide --
+# ---- the reference's OWN guide programs, unchanged: the reference checkout's test/guide/{primer,group_sort}.cc are compiled where
+# they lie (nothing is copied) against -I<repo>/include and linked with libssgpu; the binaries are built into oracle/_ref/ by
+# __graft_entry__.build() where the reference exists and travel to the GPU machine with the tree, where they RUN: every TEST of the guide --
 # bound a + b, Compute, Filter, grouped aggregates with STRING + BOOL keys, Sort drained 1024 rows at a time into a Block
 # through ViewCopier -- must pass against the MI355X library ------------------------------------------------------------
-sys.path.insert(0, os.path.join(ROOT, "tests", "cpp"))
-import build_ref_guides  # noqa: E402
+from oracle import build_ref_guides  # noqa: E402
 
 
 @pytest.mark.parametrize("name", build_ref_guides.GUIDES)
 def test_reference_guide_compiles_and_links_unchanged(name):
     if not os.path.exists(build_ref_guides.source(name)):
-        pytest.skip("no reference checkout here (the GPU box): the binary built in the build container is what runs")
+        pytest.skip("no reference checkout here (the GPU machine): the binary build() left in oracle/_ref/ is what runs")
     out = build_ref_guides.build(name)
     assert out and os.access(out, os.X_OK)
     # and under -Wall -Werror as a pure syntax check of the facade's surface the guide touches
@@ -96,15 +94,14 @@ def test_reference_guide_compiles_and_links_unchanged(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", build_ref_guides.GUIDES)
 def test_reference_guide_runs_green(name):
-    """The binary is built where a reference checkout exists (the build container, __graft_entry__.build()) and travels to the GPU box
-    with the other built artefacts.  build() leaves tests/cpp/_build/EXPECTED next to it: where that file (or SSGPU_EXPECT_REF_GUIDES=1)
-    says the binaries were built, a missing one FAILS -- a skip here would read as a pass.  What ran is appended to
-    gpurun_out/ref_guides_ran.txt (copied into profiles/ with the round's other evidence)."""
+    """The binary is built where a reference checkout exists (__graft_entry__.build(), into oracle/_ref/) and travels to the GPU machine
+    with the tree.  build() leaves oracle/_ref/EXPECTED next to it: where that file (or SSGPU_EXPECT_REF_GUIDES=1) says the binaries
+    were built, a missing one FAILS -- a skip here would read as a pass."""
     out = build_ref_guides.build(name) or build_ref_guides.binary(name)
     expected = os.environ.get("SSGPU_EXPECT_REF_GUIDES") == "1" or name in build_ref_guides.expected()
     if not os.path.exists(out):
-        assert not expected, "tests/cpp/_build/ref_guide_%s is expected (tests/cpp/_build/EXPECTED / SSGPU_EXPECT_REF_GUIDES) and missing" % name
-        pytest.skip("tests/cpp/_build/ref_guide_%s was not built (no reference checkout where this tree was built)" % name)
+        assert not expected, "oracle/_ref/ref_guide_%s is expected (oracle/_ref/EXPECTED / SSGPU_EXPECT_REF_GUIDES) and missing" % name
+        pytest.skip("oracle/_ref/ref_guide_%s was not built (no reference checkout where this tree was built)" % name)
     p = subprocess.run([out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
     assert p.returncode == 0 and "[  PASSED  ]" in p.stdout and "FAILED" not in p.stdout, p.stdout[-4000:]
     try:

@@ -87,10 +87,15 @@ def run_job(job):
     return json.loads(lines[-1])
 
 
+# processes that may hold the GPU at once on the machines the suite runs on; this (pytest) process holds it too
+MAX_GPU_PROCESSES = 16
+
+
 @pytest.fixture(scope="module")
 def corpus():
     work = jobs()
     workers = int(os.environ.get("SS_FUZZ_WORKERS", "0")) or max(4, min(48, cpu_quota() or (os.cpu_count() or 8) // 4))
+    workers = min(workers, MAX_GPU_PROCESSES - 1)
     with concurrent.futures.ThreadPoolExecutor(workers) as pool:
         results = list(pool.map(run_job, [j for _leg, j in work]))
     legs = {}

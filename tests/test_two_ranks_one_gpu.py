@@ -163,7 +163,7 @@ def test_bench_py_takes_its_multi_rank_path_with_two_ranks_on_one_gpu(query, ext
     env = dict(os.environ, SSGPU_BENCH_SHARE_GPU="1")
     env.pop("SSGPU_SPECIALIZE", None); env.pop("SSGPU_GROUP_DENSE", None)      # (the library's own defaults, as in the driver's run)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "1000000", "--query", query, "--no-cpu-baseline"] + extra
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "1000000", "--query", query, "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -7,12 +7,12 @@ OUT=$REPO/gpurun_out/pmc_$tag
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $OUT/$c -o p -- python $REPO/bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline > $OUT/$c.log 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $OUT/$c -o p -- python $REPO/bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline > $OUT/$c.log 2>&1
 done
 python - "$OUT" "$tag" "$*" <<'PY'
 import csv, glob, json, sys, collections
 out, tag, args = sys.argv[1], sys.argv[2], sys.argv[3]
-res = {"tag": tag, "command": "python bench.py %s --steps 5 --warmup 2 --no-cpu-baseline" % args, "kernels": {}}
+res = {"tag": tag, "command": "python bench.py --full %s --steps 5 --warmup 2 --no-cpu-baseline" % args, "kernels": {}}
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
     f = glob.glob(out + "/%s/**/*counter_collection.csv" % c, recursive=True)
     acc = collections.defaultdict(list)

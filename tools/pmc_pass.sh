@@ -8,7 +8,7 @@ for grp in "$@"; do
   i=$((i+1))
   out=$REPO/gpurun_out/pmc/g$i
   rm -rf $out; mkdir -p $out
-  rocprofv3 --pmc $grp --output-format csv -d $out -o p -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $out/log.txt 2>&1
+  rocprofv3 --pmc $grp --output-format csv -d $out -o p -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $out/log.txt 2>&1
   f=$(find $out -name "*counter_collection.csv" | head -1)
   python - "$f" <<'PY'
 import csv, sys, collections

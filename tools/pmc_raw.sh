@@ -10,7 +10,7 @@ IFS=';' read -ra GROUPS_ <<< "$groups"
 i=0
 for grp in "${GROUPS_[@]}"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $grp --output-format csv -d $OUT/g$i -o p -- python $REPO/bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline > $OUT/g$i.log 2>&1 || echo "pass $i ($grp) failed" >> $OUT/failed.txt
+  timeout 600 rocprofv3 --pmc $grp --output-format csv -d $OUT/g$i -o p -- python $REPO/bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline > $OUT/g$i.log 2>&1 || echo "pass $i ($grp) failed" >> $OUT/failed.txt
 done
 python3 - "$OUT" "$tag" "$*" <<'PY'
 import csv, glob, json, sys, collections
@@ -20,7 +20,7 @@ for f in glob.glob(out + "/g*/**/*counter_collection.csv", recursive=True):
     for row in csv.DictReader(open(f)):
         if "ssgpu" in row["Kernel_Name"]:
             acc[row["Kernel_Name"].split("(")[0]][row["Counter_Name"]].append(float(row["Counter_Value"]))
-res = {"tag": tag, "command": "python bench.py %s --steps 5 --warmup 2 --no-cpu-baseline" % args, "kernels": {}}
+res = {"tag": tag, "command": "python bench.py --full %s --steps 5 --warmup 2 --no-cpu-baseline" % args, "kernels": {}}
 for k, cs in acc.items():
     for c, v in cs.items():
         v = sorted(v)[len(v) // 4:]

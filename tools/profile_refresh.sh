@@ -9,8 +9,8 @@ cd /tmp && export TMPDIR=/tmp
 for q in wide group3 group sort filter_mat; do
   mkdir -p $OUT/$q
   extra="--no-cpu-baseline"; [ $q = wide ] && extra=""
-  timeout 150 python $REPO/bench.py --query $q $extra > $OUT/$q/line.json 2> $OUT/$q/line.err
-  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$q/stats -o k -- python $REPO/bench.py --query $q --steps 50 --warmup 5 --no-cpu-baseline > $OUT/$q/stats.log 2>&1
+  timeout 150 python $REPO/bench.py --full --query $q $extra > $OUT/$q/line.json 2> $OUT/$q/line.err
+  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$q/stats -o k -- python $REPO/bench.py --full --query $q --steps 50 --warmup 5 --no-cpu-baseline > $OUT/$q/stats.log 2>&1
   f=$(find $OUT/$q/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/$q/kernel_stats.csv
   rm -rf $OUT/$q/stats
   tail -c 300 $OUT/$q/line.json; echo

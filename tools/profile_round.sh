@@ -6,10 +6,10 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$R
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py > $OUT/bench_line.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $R -- python $REPO/bench.py --no-cpu-baseline > $OUT/stats.log 2>&1
+python $REPO/bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $R -- python $REPO/bench.py --full --no-cpu-baseline > $OUT/stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -o p -- python $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_$c.log 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -o p -- python $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_$c.log 2>&1
 done
 python - "$OUT" "$R" <<'PY'
 import csv, glob, json, sys
@@ -24,7 +24,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
     vals[c] = (sum(acc) / len(acc), len(acc))
 line = json.loads(open(out + "/bench_line.json").read().strip().splitlines()[-1])
 alg = line["roofline"]["algorithmic_bytes_per_row"] * line["config"]["rows_per_gpu"]
-j = {"round": r, "kernel": "ssgpu_pipeline_kernel<1, false>", "command": "python bench.py --steps 5 --warmup 1 --no-cpu-baseline",
+j = {"round": r, "kernel": "ssgpu_pipeline_kernel<1, false>", "command": "python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline",
      "FETCH_SIZE_KiB_per_launch": vals["FETCH_SIZE"][0], "WRITE_SIZE_KiB_per_launch": vals["WRITE_SIZE"][0],
      "launches_sampled": vals["FETCH_SIZE"][1],
      "correction": "FETCH_SIZE x2 on gfx950 for 16 B/lane streaming reads (MI355X_MICROARCH.md, HBM)",

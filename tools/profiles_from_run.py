@@ -81,7 +81,7 @@ def main():
                 total += fk * 1024 * ff + wk * 1024
             alg = line["roofline"]["algorithmic_bytes_per_row"] * line["config"]["rows_per_gpu"]
             traffic = total
-            j = {"round": ROUND, "query": q, "command": "python bench.py --query %s --steps 5 --warmup 2 --no-cpu-baseline" % q,
+            j = {"round": ROUND, "query": q, "command": "python bench.py --full --query %s --steps 5 --warmup 2 --no-cpu-baseline" % q,
                  "kernels": per_kernel, "correction": "FETCH_SIZE x 2 for streaming kernels (gfx950: the counter tallies 128-byte requests at 64 bytes; measured 2.000 for 4 / 8 / 16 B-per-lane "
                                                       "reads and 40-byte records), x 1 for the Sort's record gather (random 64-byte reads are 64-byte requests: measured 1.000, "
                                                       "profiles/r04_pmc_gather_calibration.json), WRITE_SIZE x 1 (measured 1.000)",
