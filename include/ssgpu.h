@@ -326,7 +326,6 @@ int ssgpu_ctx_synchronize(ssgpu_ctx* ctx);
  *                           grid_limit
  *   runtime specialisation: specialize (1 = plans created afterwards run kernels compiled for them, see ssgpu_plan_specialize;
  *                           0 = only plans that call ssgpu_plan_specialize; default 0)
- *   Filter:                 filter_single_pass (1 = decoupled look-back instead of count + store passes)
  *   GroupAggregate:         group_capacity (initial table), group_local (0 = no LDS table in front of the global one),
  *                           group_partition (0 never / 1 by run feedback / 2 always hash-partitioned), group_slab (0 never /
  *                           1 by estimate / 2 always the one-table-per-CU form), group_resident (0 = the one-table-per-CU form always
@@ -334,14 +333,11 @@ int ssgpu_ctx_synchronize(ssgpu_ctx* ctx);
  *                           the direct shape over a 1/64 prefix, result discarded -- ahead of a plan's first run over >= group_scout_rows rows; group_scout_rows: 8 M by default, a plan that is run ONCE over fewer rows may lower it --
  *                           an eighth of a smaller input is scouted --, trading a faster first run for a coarser group-count estimate), part_plain (0 = the partition scatter always as
  *                           a VM program, never as its own kernel), part_n, part_wgs_per_cu, part_lds_target, part_agg_lds,
- *                           part_rec_align, lazy_feedback (0 = a GroupAggregate reads its overflow / feedback words at the end of EVERY run --
+ *                           lazy_feedback (0 = a GroupAggregate reads its overflow / feedback words at the end of EVERY run --
  *                           one stream synchronise per run -- instead of leaving them to the next touch of the result; see ssgpu_plan_run)
  *                           plain partition scatter (ABI 10): pscat_pipe (0 = the tile-after-tile loop instead of the software pipeline of the
  *                           specialised build), pscat_threads / pscat_rows / pscat_wgs (launch shape: 512 / 1024 threads, rows per thread,
- *                           workgroups per CU; 0 = 1024 x 2 x 1), part_split (1 = dense partitions' records as payload words + 16-bit table
- *                           entries), part_prefetch (0 = the partition aggregation loads its records in the trip that uses them),
- *                           part_overlap / part_overlap_rows (> 1: a dense run over at least that many rows takes its input in that many
- *                           row ranges, range k aggregated on a side stream beside the scatter of range k + 1; measured slower, default 1)
+ *                           workgroups per CU; 0 = 1024 x 2 x 1), part_prefetch (0 = the partition aggregation loads its records in the trip that uses them)
  *   ScalarAggregate:        fuse_emit (0 = the result row is emitted by a launch of its own instead of the finish launch)
  *   results:                out_arena (0 = one allocation per column of a stage's large result instead of one arena with skewed bases)
  *   stage hand-off:         async_handoff (0 = the row count of every intermediate result is read on the host before the next stage is launched;
@@ -350,8 +346,7 @@ int ssgpu_ctx_synchronize(ssgpu_ctx* ctx);
  *                           sort_hi_digits (2..4, 0 = by row count), sort_compact (0 = (key, row id) pairs instead of one
  *                           (high half | row id) word)
  *   measurement:            profile, profile_total (HIP events around the stage kernels / the run: ssgpu_plan_counters,
- *                           ssgpu_plan_recent_kernel_ms), debug_timing
- *   development only (results may be WRONG): part_scatter_debug, part_agg_debug */
+ *                           ssgpu_plan_recent_kernel_ms), debug_timing */
 int ssgpu_ctx_set_option(ssgpu_ctx* ctx, const char* key, int64_t value);
 
 /* ---- pinned host memory (BufferAllocator seam, memory.h:100-233) -------- */
@@ -536,9 +531,7 @@ typedef struct ssgpu_stage_info {
   int32_t hot_keys;         /* heavy-hitter keys the stage aggregates apart from the hash partitions (found when a segment overflowed; ABI 6) */
   int32_t dense_slots;      /* > 0: the group tables are indexed by the key columns' value ranges (dense slots, ABI 7) -- this many slots; group_shape
                                then says how they are filled: 1 partitions of slot ranges, 3 one table fed from the input columns */
-  int32_t split_records;    /* dense partitions: the last run's records left the scatter as payload words + 16-bit table entries (no index word) */
-  int32_t row_ranges;       /* dense partitions: row ranges the last run took its input in -- range k is aggregated on a side stream while range k + 1 is scattered (1: one range, no overlap) */
-  int32_t reserved[2];
+  int32_t reserved[4];
 } ssgpu_stage_info;
 int32_t ssgpu_plan_stage_count(const ssgpu_plan* plan);
 int ssgpu_plan_stage_info(const ssgpu_plan* plan, int32_t stage, ssgpu_stage_info* out);

@@ -132,8 +132,7 @@ struct Stage {
   Schema in_schema;     // schema of the stage input (plan input or previous stage's result)
   Schema out_schema;
   Program main;         // the pipeline program
-  Program count_pass;   // STAGE_MATERIALIZE with a filter, two-pass form: predicate + SEL_COUNT
-  bool single_pass = false;   // STAGE_MATERIALIZE with a filter: SEL_RANK_LB + STOREG (no count pass)
+  Program count_pass;   // STAGE_MATERIALIZE with a filter: predicate + SEL_COUNT
   bool has_filter = false;
   std::vector<AggOut> aggs;               // SCALAR_AGG / GROUP_AGG (out_schema order, after keys)
   std::vector<GroupKeyField> group_keys;  // GROUP_AGG
@@ -212,8 +211,6 @@ struct PlanDesc {
   std::vector<ssgpu_agg> aggs;
   std::vector<ssgpu_sortkey> sortkeys;
   std::vector<std::string> strings;  // storage for all names (stable addresses)
-  bool filter_single_pass = false;   // ctx option of the same name at plan creation (lower.cpp, finish_materialize)
-  int part_rec_align = 0;            // ctx option: partition records padded to a multiple of this many bytes (0 = 8)
   // the reference keeps a NaN that is a group's FIRST non-NULL value as its floating MIN / MAX (aggregation_operators.h:189-228):
   // in this form every such aggregate gets a hidden FIRST of the same column and the result is IF(IS_NAN(first), first, min).
   // Set by the runtime when a run met a NaN in a floating MIN / MAX (SSGPU_FLAG_NAN_IN_MINMAX); plans start without it.

@@ -34,8 +34,6 @@
 #define PS_REC_INV kPsRecInv
 #define PS_NPARTS kPsNParts
 #define PS_DENSE (kPsDense != 0u)
-#define PS_SPLIT (kPsSplit != 0u)
-#define PS_PAY_INV kPsPayInv
 #define PS_UNROLL _Pragma("unroll")
 #else
 #define PS_NKEYS P.n_keys
@@ -54,22 +52,8 @@
 #define PS_REC_INV P.rec_inv
 #define PS_NPARTS P.n_parts
 #define PS_DENSE (P.dense.on != 0u)
-#define PS_SPLIT (P.split != 0u)
-#define PS_PAY_INV P.pay_inv
 #define PS_UNROLL
 #endif
-// Input columns are read once and never again; non-temporal loads (-DPS_NT=1) were meant to keep them from pushing the half-written
-// record lines out of the XCD's L2.  Measured (profiles/r06_split_ab.txt): config #3 2.60 -> 2.73 ms, config #4 unchanged: off.
-#ifndef PS_NT
-#define PS_NT 0
-#endif
-template <typename T> __device__ __forceinline__ T ps_ld(const T* p) {
-#if PS_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
 
 typedef unsigned long long u64;
 typedef long long i64;
@@ -103,13 +87,13 @@ __device__ __forceinline__ bool pscat_pred(const void* data, const u8* nulls, u6
   const bool is_null = nulls ? nulls[row] != 0 : false;    // a NULL predicate drops the row (filter.cc:170-199)
   bool lt, gt, eq;   // column < constant, column > constant, column == constant
   switch (kind) {
-    case 0: { const i32 v = ps_ld(reinterpret_cast<const i32*>(data) + row), k = (i32)(u32)c; lt = v < k; gt = v > k; eq = v == k; } break;
-    case 1: { const u32 v = ps_ld(reinterpret_cast<const u32*>(data) + row), k = (u32)c; lt = v < k; gt = v > k; eq = v == k; } break;
-    case 2: { const i64 v = ps_ld(reinterpret_cast<const i64*>(data) + row), k = (i64)c; lt = v < k; gt = v > k; eq = v == k; } break;
-    case 3: { const u64 v = ps_ld(reinterpret_cast<const u64*>(data) + row), k = c; lt = v < k; gt = v > k; eq = v == k; } break;
-    case 4: { const float v = ps_ld(reinterpret_cast<const float*>(data) + row), k = __uint_as_float((u32)c); lt = v < k; gt = v > k; eq = v == k; } break;
-    case 6: { const u8 v = ps_ld(reinterpret_cast<const u8*>(data) + row), k = (u8)c; lt = v < k; gt = v > k; eq = v == k; } break;   // a BOOL column as the predicate: (column != FALSE)
-    default: { const double v = ps_ld(reinterpret_cast<const double*>(data) + row), k = u2d(c); lt = v < k; gt = v > k; eq = v == k; } break;
+    case 0: { const i32 v = reinterpret_cast<const i32*>(data)[row], k = (i32)(u32)c; lt = v < k; gt = v > k; eq = v == k; } break;
+    case 1: { const u32 v = reinterpret_cast<const u32*>(data)[row], k = (u32)c; lt = v < k; gt = v > k; eq = v == k; } break;
+    case 2: { const i64 v = reinterpret_cast<const i64*>(data)[row], k = (i64)c; lt = v < k; gt = v > k; eq = v == k; } break;
+    case 3: { const u64 v = reinterpret_cast<const u64*>(data)[row], k = c; lt = v < k; gt = v > k; eq = v == k; } break;
+    case 4: { const float v = reinterpret_cast<const float*>(data)[row], k = __uint_as_float((u32)c); lt = v < k; gt = v > k; eq = v == k; } break;
+    case 6: { const u8 v = reinterpret_cast<const u8*>(data)[row], k = (u8)c; lt = v < k; gt = v > k; eq = v == k; } break;   // a BOOL column as the predicate: (column != FALSE)
+    default: { const double v = reinterpret_cast<const double*>(data)[row], k = u2d(c); lt = v < k; gt = v > k; eq = v == k; } break;
   }
   bool r;
   switch (cmp) {
@@ -121,14 +105,6 @@ __device__ __forceinline__ bool pscat_pred(const void* data, const u8* nulls, u6
   return r && !is_null;
 }
 
-#ifndef PS_PAIR_LOADS
-#define PS_PAIR_LOADS 0     /* 1: the pipelined form with two rows per thread loads pairs of consecutive rows (A/B: profiles/r06_pair_loads.txt) */
-#endif
-#if PS_PAIR_LOADS
-#define PS_ROW(base, j, t) ((R) == 2 ? (base) + 2ull * (t) + (u64)(j) : (base) + (u64)(j) * THREADS + (t))
-#else
-#define PS_ROW(base, j, t) ((base) + (u64)(j) * THREADS + (t))
-#endif
 #ifdef SSGPU_RTC_PSCAT
 // the same predicate on a value that is already in a register (the pipelined form loads a tile's columns one tile ahead)
 __device__ __forceinline__ bool pscat_pred_value(u64 raw, bool is_null, u64 c, u32 kind, u32 cmp, bool col_on_left) {
@@ -152,7 +128,7 @@ __device__ __forceinline__ bool pscat_pred_value(u64 raw, bool is_null, u64 c, u
   return r && !is_null;
 }
 __device__ __forceinline__ u64 pscat_load_width(const void* p, u32 width, u64 row) {
-  return width == 8u ? ps_ld(reinterpret_cast<const u64*>(p) + row) : width == 4u ? (u64)ps_ld(reinterpret_cast<const u32*>(p) + row) : (u64)ps_ld(reinterpret_cast<const u8*>(p) + row);
+  return width == 8u ? reinterpret_cast<const u64*>(p)[row] : width == 4u ? (u64)reinterpret_cast<const u32*>(p)[row] : (u64)reinterpret_cast<const u8*>(p)[row];
 }
 #endif
 
@@ -205,43 +181,9 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
     struct St { u64 key[R]; u32 pt[R], pos[R]; bool ok[R]; u64 fv[R][REGF]; };
     auto issue = [&](u64 tile, Raw& W) {
       const u64 base = tile * T;
-#if PS_PAIR_LOADS
-      // (-DPS_PAIR_LOADS=1, two rows per thread) a thread takes two CONSECUTIVE rows of the tile, so that an 8-byte column leaves
-      // memory as 16 bytes per lane and a 4-byte one as 8; which rows of a tile a thread holds is immaterial to everything downstream
-      if constexpr (R == 2) {
-        typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-        typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-        const u64 row0 = base + 2ull * t;
-        const bool both = tile < n_tiles && row0 + 1ull < n;
-        if (both) {
-          W.in[0] = W.in[1] = true;
-#pragma unroll
-          for (u32 q = 0; q < kPsNPreds; ++q) {
-            const u32 pw = kPsPredKind[q] == 6u ? 1u : (kPsPredKind[q] == 0u || kPsPredKind[q] == 1u || kPsPredKind[q] == 4u) ? 4u : 8u;
-            if (pw == 8u) { const u64x2 v = *reinterpret_cast<const u64x2*>(reinterpret_cast<const u64*>(P.preds[q].data) + row0); W.p[0][q] = v.x; W.p[1][q] = v.y; }
-            else if (pw == 4u) { const u32x2 v = *reinterpret_cast<const u32x2*>(reinterpret_cast<const u32*>(P.preds[q].data) + row0); W.p[0][q] = v.x; W.p[1][q] = v.y; }
-            else { W.p[0][q] = reinterpret_cast<const u8*>(P.preds[q].data)[row0]; W.p[1][q] = reinterpret_cast<const u8*>(P.preds[q].data)[row0 + 1]; }
-            W.pn[0][q] = P.preds[q].nulls ? (u32)P.preds[q].nulls[row0] : 0u; W.pn[1][q] = P.preds[q].nulls ? (u32)P.preds[q].nulls[row0 + 1] : 0u;
-          }
-#pragma unroll
-          for (u32 k = 0; k < kPsNKeys; ++k) {
-            if (kPsKeyWidth[k] == 8u) { const u64x2 v = *reinterpret_cast<const u64x2*>(reinterpret_cast<const u64*>(P.keys[k].data) + row0); W.k[0][k] = v.x; W.k[1][k] = v.y; }
-            else if (kPsKeyWidth[k] == 4u) { const u32x2 v = *reinterpret_cast<const u32x2*>(reinterpret_cast<const u32*>(P.keys[k].data) + row0); W.k[0][k] = v.x; W.k[1][k] = v.y; }
-            else { W.k[0][k] = reinterpret_cast<const u8*>(P.keys[k].data)[row0]; W.k[1][k] = reinterpret_cast<const u8*>(P.keys[k].data)[row0 + 1]; }
-            W.kn[0][k] = P.keys[k].nulls ? (u32)P.keys[k].nulls[row0] : 0u; W.kn[1][k] = P.keys[k].nulls ? (u32)P.keys[k].nulls[row0 + 1] : 0u;
-          }
-#pragma unroll
-          for (u32 f = 0; f < REGF; ++f) {
-            if (f < nf && PS_FIELD_WIDTH(f < nf ? f : 0u) == 8u && P.fields[f].src) { const u64x2 v = *reinterpret_cast<const u64x2*>(reinterpret_cast<const u64*>(P.fields[f].src) + row0); W.f[0][f] = v.x; W.f[1][f] = v.y; }
-            else { W.f[0][f] = 0ull; W.f[1][f] = 0ull; }
-          }
-          return;
-        }
-      }
-#endif
 #pragma unroll
       for (int j = 0; j < R; ++j) {
-        const u64 row = PS_ROW(base, j, t);
+        const u64 row = base + (u64)j * THREADS + t;
         W.in[j] = tile < n_tiles && row < n;
         const u64 rowc = W.in[j] ? row : 0ull;     // (unconditional loads, on a row that exists)
 #pragma unroll
@@ -256,7 +198,7 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
         }
 #pragma unroll
         for (u32 f = 0; f < REGF; ++f)
-          W.f[j][f] = (f < nf && PS_FIELD_WIDTH(f < nf ? f : 0u) == 8u && P.fields[f].src) ? ps_ld(reinterpret_cast<const u64*>(P.fields[f].src) + rowc) : 0ull;
+          W.f[j][f] = (f < nf && PS_FIELD_WIDTH(f < nf ? f : 0u) == 8u && P.fields[f].src) ? reinterpret_cast<const u64*>(P.fields[f].src)[rowc] : 0ull;
       }
     };
     bool miss = false, over = false;
@@ -288,8 +230,8 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
           const bool in = ssgpu_dense_index(P.dense, key, &idx);
           if (ok && !in) miss = true;
           ok = ok && in;
-          const u32 entry = ssgpu_dense_entry(P.dense, idx, &pt);
-          key = PS_SPLIT ? (u64)entry : (u64)idx;
+          ssgpu_dense_entry(P.dense, idx, &pt);
+          key = idx;
         } else pt = part_of(key, NP);
         S.key[j] = key; S.pt[j] = pt; S.ok[j] = ok; S.pos[j] = 0u;
         if (ok) S.pos[j] = atomicAdd(&c[pt], 1u);
@@ -338,7 +280,7 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
       const u64 base = tile * T;
 #pragma unroll
       for (int j = 0; j < R; ++j) {
-        const u64 row = PS_ROW(base, j, t);
+        const u64 row = base + (u64)j * THREADS + t;
         const bool ok = cur.ok[j];
         const u64 rowc = ok ? row : 0ull;
         const u32 pt = cur.pt[j];
@@ -352,9 +294,9 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
         for (u32 f = 0; f < nf; ++f) {
           const u32 fw = PS_FIELD_WIDTH(f), fo = PS_FIELD_OFF(f);
           const void* src = P.fields[f].src;
-          if (fw == 8u) { if (f >= REGF) { const u64 v = src ? ps_ld(reinterpret_cast<const u64*>(src) + rowc) : 0ull; if (ok) *reinterpret_cast<u64*>(r + fo) = v; } }
-          else if (fw == 4u) { const u32 v = src ? ps_ld(reinterpret_cast<const u32*>(src) + rowc) : 0u; if (ok) *reinterpret_cast<u32*>(r + fo) = v; }
-          else { const u8 v = src ? ps_ld(reinterpret_cast<const u8*>(src) + rowc) : (u8)0; if (ok) *reinterpret_cast<u8*>(r + fo) = v; }
+          if (fw == 8u) { if (f >= REGF) { const u64 v = src ? reinterpret_cast<const u64*>(src)[rowc] : 0ull; if (ok) *reinterpret_cast<u64*>(r + fo) = v; } }
+          else if (fw == 4u) { const u32 v = src ? reinterpret_cast<const u32*>(src)[rowc] : 0u; if (ok) *reinterpret_cast<u32*>(r + fo) = v; }
+          else { const u8 v = src ? reinterpret_cast<const u8*>(src)[rowc] : (u8)0; if (ok) *reinterpret_cast<u8*>(r + fo) = v; }
         }
       }
       St nxt;
@@ -363,24 +305,11 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
       scan_reserve(c_nxt);
       issue(tile + 2u * step, raw);
       const u64* sw = reinterpret_cast<const u64*>(stage);
-      if (PS_SPLIT) {
-        const u32 pw = wpr - 1u, pwords = nrec * pw;
-        for (u32 w = t; w < pwords; w += THREADS) {
-          const u32 j = pw == 1u ? w : __umulhi(w, PS_PAY_INV), f = w - j * pw;
-          const u32 g = grec[j];
-          if (g != VM_NONE) P.recs[(u64)g * pw + f] = sw[j * wpr + 1u + f];
-        }
-        for (u32 j = t; j < nrec; j += THREADS) {
-          const u32 g = grec[j];
-          if (g != VM_NONE) P.recs_entry[g] = (unsigned short)sw[j * wpr];
-        }
-      } else {
-        const u32 words = nrec * wpr;
-        for (u32 w = t; w < words; w += THREADS) {
-          const u32 j = wpr == 1u ? w : __umulhi(w, PS_REC_INV), f = w - j * wpr;
-          const u32 g = grec[j];
-          if (g != VM_NONE) P.recs[(u64)g * wpr + f] = sw[w];
-        }
+      const u32 words = nrec * wpr;
+      for (u32 w = t; w < words; w += THREADS) {
+        const u32 j = wpr == 1u ? w : __umulhi(w, PS_REC_INV), f = w - j * wpr;
+        const u32 g = grec[j];
+        if (g != VM_NONE) P.recs[(u64)g * wpr + f] = sw[w];
       }
       cur = nxt; par ^= 1u;
     }
@@ -402,15 +331,15 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
       key[j] = 0ull;
       PS_UNROLL for (u32 k = 0; k < PS_NKEYS; ++k) {
         const u32 kw = PS_KEY_WIDTH(k), kbits = PS_KEY_BITS(k), kshift = PS_KEY_SHIFT(k);
-        u64 a = kw == 8 ? ps_ld(reinterpret_cast<const u64*>(P.keys[k].data) + rowc) : kw == 4 ? (u64)ps_ld(reinterpret_cast<const u32*>(P.keys[k].data) + rowc)
-                                                                                       : (u64)ps_ld(reinterpret_cast<const u8*>(P.keys[k].data) + rowc);
+        u64 a = kw == 8 ? reinterpret_cast<const u64*>(P.keys[k].data)[rowc] : kw == 4 ? (u64)reinterpret_cast<const u32*>(P.keys[k].data)[rowc]
+                                                                                       : (u64)reinterpret_cast<const u8*>(P.keys[k].data)[rowc];
         a &= kbits >= 64 ? ~0ull : ((1ull << kbits) - 1ull);
         if (P.keys[k].nulls && P.keys[k].nulls[rowc]) a = 1ull << (PS_KEY_NULLBIT(k) - kshift);
         key[j] |= a << kshift;
       }
 #pragma unroll
       for (u32 f = 0; f < REGF; ++f)   // the leading 8-byte fields travel through registers: their loads are in flight during the ranking
-        fv[j][f] = (f < nf && PS_FIELD_WIDTH(f < nf ? f : 0u) == 8u && P.fields[f].src) ? ps_ld(reinterpret_cast<const u64*>(P.fields[f].src) + rowc) : 0ull;
+        fv[j][f] = (f < nf && PS_FIELD_WIDTH(f < nf ? f : 0u) == 8u && P.fields[f].src) ? reinterpret_cast<const u64*>(P.fields[f].src)[rowc] : 0ull;
       // heavy hitters are aggregated by the resident kernel (hot_only), not scattered: one key must not fill a partition's segments
       if (P.n_hot) {   // (uniform)
         u32 i = hash_local(key[j]) & (SSGPU_HOT_SLOTS - 1u);
@@ -426,8 +355,8 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
         const bool in = ssgpu_dense_index(P.dense, key[j], &idx);
         if (ok[j] && !in) miss = true;
         ok[j] = ok[j] && in;
-        const u32 entry = ssgpu_dense_entry(P.dense, idx, &pt[j]);
-        key[j] = PS_SPLIT ? (u64)entry : (u64)idx;   // (split records: the partition's table entry, 16 bits in an array of its own)
+        ssgpu_dense_entry(P.dense, idx, &pt[j]);
+        key[j] = idx;
       } else
       pt[j] = part_of(key[j], NP);
       pos[j] = 0u;
@@ -462,9 +391,9 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
       PS_UNROLL for (u32 f = 0; f < nf; ++f) {
         const u32 fw = PS_FIELD_WIDTH(f), fo = PS_FIELD_OFF(f);
         const void* src = P.fields[f].src;
-        if (fw == 8u) { if (f >= REGF) { const u64 v = src ? ps_ld(reinterpret_cast<const u64*>(src) + rowc) : 0ull; if (ok[j]) *reinterpret_cast<u64*>(r + fo) = v; } }
-        else if (fw == 4u) { const u32 v = src ? ps_ld(reinterpret_cast<const u32*>(src) + rowc) : 0u; if (ok[j]) *reinterpret_cast<u32*>(r + fo) = v; }
-        else { const u8 v = src ? ps_ld(reinterpret_cast<const u8*>(src) + rowc) : (u8)0; if (ok[j]) *reinterpret_cast<u8*>(r + fo) = v; }
+        if (fw == 8u) { if (f >= REGF) { const u64 v = src ? reinterpret_cast<const u64*>(src)[rowc] : 0ull; if (ok[j]) *reinterpret_cast<u64*>(r + fo) = v; } }
+        else if (fw == 4u) { const u32 v = src ? reinterpret_cast<const u32*>(src)[rowc] : 0u; if (ok[j]) *reinterpret_cast<u32*>(r + fo) = v; }
+        else { const u8 v = src ? reinterpret_cast<const u8*>(src)[rowc] : (u8)0; if (ok[j]) *reinterpret_cast<u8*>(r + fo) = v; }
       }
     }
     if (over) atomicExch(P.overflow, 1u);
@@ -472,22 +401,6 @@ __global__ __launch_bounds__(NT) void ssgpu_part_scatter_plain_kernel(const Plai
     for (u32 i = t; i < NP; i += THREADS) cnt[i] = 0u;   // (read last before the barrier above; next written after the one below)
     __syncthreads();
     const u64* sw = reinterpret_cast<const u64*>(stage);
-    if (PS_SPLIT) {
-      // split records (dense slots): the payload words of a record -- everything behind its key word -- go to the segment's record
-      // array, (wpr - 1) words each, and the key word, which here is the entry of the partition's table (< 2^16), to the segment's
-      // array of 16-bit entries: 34 bytes per row for four DOUBLE inputs where the whole record took 40
-      const u32 pw = wpr - 1u, nrec = start[NP], pwords = nrec * pw;
-      for (u32 w = t; w < pwords; w += THREADS) {
-        const u32 j = pw == 1u ? w : __umulhi(w, PS_PAY_INV), f = w - j * pw;
-        const u32 g = grec[j];
-        if (g != VM_NONE) P.recs[(u64)g * pw + f] = sw[j * wpr + 1u + f];
-      }
-      for (u32 j = t; j < nrec; j += THREADS) {
-        const u32 g = grec[j];
-        if (g != VM_NONE) P.recs_entry[g] = (unsigned short)sw[j * wpr];
-      }
-      continue;   // (as below: no barrier needed before the next tile)
-    }
     const u32 words = start[NP] * wpr;
     for (u32 w = t; w < words; w += THREADS) {
       const u32 j = wpr == 1u ? w : __umulhi(w, PS_REC_INV), f = w - j * wpr;   // (one-word records -- the key alone, COUNT(*) queries: 2^32 / 1 + 1 does not fit rec_inv)

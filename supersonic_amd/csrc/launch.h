@@ -76,7 +76,6 @@ struct PartAggParams {
   unsigned int local_capacity;        // LDS table entries per partition
   unsigned int n_gaggs;               // accumulator words per group
   unsigned int n_aggs, any_cnt;
-  unsigned int debug;                 // development switches (perf attribution): 1 = no aggregation, 2 = no probe
   unsigned int slab_segs;             // 0: workgroup = hash partition (its table is dumped to its own slots of T).  > 0: ONE
                                       // partition; workgroup j aggregates segments [j * slab_segs, (j + 1) * slab_segs) -- a slab of
                                       // the rows -- in a table that holds EVERY group, and merges it into T with atomics
@@ -91,13 +90,6 @@ struct PartAggParams {
   // merged into global slot hot_base + e (dense slots behind the partitions' ranges) instead of a hashed slot.
   unsigned int hot_only, hot_base;
   DenseKeyMap dense;                  // dense.on: word 0 of a record is the group's dense index, not its packed key
-  // split records (PlainScatterParams::split): `recs` holds (rec_words - 1) payload words per record, word 0 -- the entry of this
-  // partition's table the record belongs to -- comes from recs_entry
-  const unsigned short* recs_entry;
-  unsigned int split;
-  // dense partitions, the input taken in several row ranges (the aggregation of range k runs beside the scatter of range k + 1): the
-  // partition's table starts from what the launch before it dumped into T instead of from the empty table
-  unsigned int accumulate;
 };
 hipError_t ssgpu_launch_part_agg(const PartAggParams& P, unsigned int lds_bytes, hipStream_t stream);
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)
@@ -156,13 +148,10 @@ struct PlainScatterParams {
   unsigned long long n_rows;
   unsigned int n_parts, seg_cap, rec_words, rec_inv;   // rec_inv = floor(2^32 / rec_words) + 1
   unsigned int n_keys, n_fields, n_preds;
-  unsigned int split;           // dense slots only: records leave as (rec_words - 1) payload words in `recs` + a 16-bit table entry in `recs_entry`
   struct Key { const void* data; const unsigned char* nulls; unsigned int width, shift, bits, nullbit; } keys[SSGPU_PSCAT_MAX_KEYS];
   struct Field { const void* src; unsigned int width, off; } fields[SSGPU_PSCAT_MAX_FIELDS];   // src NULL: an absent NULL mask (zeros)
   struct Pred { const void* data; const unsigned char* nulls; unsigned int kind, cmp, col_on_left, pad; unsigned long long bits; } preds[SSGPU_PSCAT_MAX_PREDS];
   unsigned long long* recs;     // n_parts * SSGPU_PSCAT_XCDS segments of seg_cap records
-  unsigned short* recs_entry;   // split: the same segments' table entries, one per record
-  unsigned int pay_inv, pad1;   // split: floor(2^32 / (rec_words - 1)) + 1
   unsigned int* counts;         // [n_parts * SSGPU_PSCAT_XCDS] records appended to each segment; zero at launch
   unsigned int* overflow;       // set when a segment ran full
   // heavy hitters: rows whose packed key is one of these are NOT scattered (ssgpu_group_resident_kernel, hot_only, aggregates them)
@@ -253,7 +242,6 @@ struct GroupInitParams {
 hipError_t ssgpu_launch_group_init(const GroupInitParams& P, hipStream_t stream);
 
 hipError_t ssgpu_launch_pipeline(const VmParams& P, int K, int grid, hipStream_t stream);
-int ssgpu_pipeline_resident_per_cu(const VmParams& P, int K);
 #ifndef __HIPCC_RTC__
 #include <string>
 // rtc.cpp: kernels specialised by runtime compilation.  The specialize calls return a HANDLE to a cached, reference-counted
@@ -266,7 +254,6 @@ hipError_t ssgpu_launch_pipeline_rtc(void* handle, const VmParams& P, int grid, 
 void* ssgpu_rtc_specialize_part_agg(int device, const unsigned long long* desc, int n_aggs, unsigned int rec_words, unsigned int n_gaggs, bool any_cnt,
                                     unsigned int lds_bytes, std::string* why, const PlainScatterParams* source = nullptr,   // source: the resident form (reads the input columns)
                                     bool dense = false,                                                                     // dense: records carry dense indices (DenseKeyMap), no probe
-                                    bool split = false,                                                                     // split: records arrive as payload words + 16-bit table entries
                                     bool prefetch = false);                                                                 // prefetch: the record form loads a trip ahead (narrow records)
 hipError_t ssgpu_launch_group_resident_rtc(void* handle, const PartAggParams& A, const PlainScatterParams& S, int grid, hipStream_t stream);
 hipError_t ssgpu_launch_part_agg_rtc(void* handle, const PartAggParams& P, hipStream_t stream);

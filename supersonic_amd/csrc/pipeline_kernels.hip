@@ -516,11 +516,6 @@ __device__ __forceinline__ void stage_units_direct(const VmParams& P, int u_begi
     }                                                                          \
   } break;
 
-#ifdef SS_STOREC_NT   /* development A/B through SSGPU_RTC_FLAGS: compacted survivors written with nontemporal stores */
-#define STOREC_ST(ptr, v) __builtin_nontemporal_store((v), (ptr))
-#else
-#define STOREC_ST(ptr, v) (*(ptr) = (v))
-#endif
 #define STOREC_OP(OPNAME, T)                                                   \
   case VM_##OPNAME: { CASE_FENCE;                                              \
     T* out = reinterpret_cast<T*>(P.outputs[I.dst].dst);                       \
@@ -528,24 +523,8 @@ __device__ __forceinline__ void stage_units_direct(const VmParams& P, int u_begi
       Valid2 m = valid_pair_(p, tile_valid, VM_NONE, I.c);          \
       auto vv = fetch2<T>(I.a, I.a_mask, p);                             \
       auto rk = lds_load2<u32>(I.b, p);                                        \
-      if (m.x) STOREC_ST(out + rk.x, vv.x);                                    \
-      if (m.y) STOREC_ST(out + rk.y, vv.y);                                    \
-    }                                                                          \
-  } break;
-
-// survivors of the tile -> output rows [base, base + cnt): lane g writes output row g, wave stores start on
-// 64-element boundaries of the OUTPUT column (full lines except at the tile's two ends)
-#define STOREG_OP(OPNAME, T)                                                   \
-  case VM_##OPNAME: { CASE_FENCE;                                              \
-    T* out = reinterpret_cast<T*>(P.outputs[I.dst].dst);                       \
-    const u32* sc = reinterpret_cast<const u32*>(smem + P.scratch_lds_off);    \
-    const u32 base = sc[40], end = base + sc[41];                              \
-    const u32* inv = reinterpret_cast<const u32*>(smem + I.b);                 \
-    for (u32 g = (base & ~63u) + (u32)tp; g < end; g += VM_COMPUTE_THREADS) {  \
-      if (g >= base) {                                                         \
-        const u32 src = inv[g - base];                                         \
-        out[g] = *reinterpret_cast<const T*>(smem + I.a + ((src * (u32)sizeof(T)) & I.a_mask)); \
-      }                                                                        \
+      if (m.x) out[rk.x] = vv.x;                                               \
+      if (m.y) out[rk.y] = vv.y;                                               \
     }                                                                          \
   } break;
 
@@ -596,11 +575,10 @@ __device__ __forceinline__ void stage_units_direct(const VmParams& P, int u_begi
     }                                                                          \
   } break;
 
-// Decoupled look-back of the single-pass compaction (SEL_RANK_LB): publishes tile `tile`'s survivor count, adds up the
+// Decoupled look-back (ssgpu_group_extract_lb_kernel): publishes tile `tile`'s survivor count, adds up the
 // counts of the earlier tiles down to the first one that already knows its inclusive prefix, publishes this tile's own
 // inclusive prefix and returns the exclusive one.  Called by wave 0 of the workgroup, all 64 lanes (lane j looks at the
-// j-th tile back).  Kept out of line: inlined into the interpreter its spin loop changes the code the compiler makes
-// for every OTHER program (the 8-column headline ran 1.58 ms instead of 1.07 ms with this loop inlined, same box).
+// j-th tile back).  Kept out of line, the form the extract kernel was measured with.
 __device__ __noinline__ u32 lookback_rows_before(unsigned long long* status, int tile, u32 run, u64 tag, unsigned int* ctrl, unsigned int* error_flag, int lane) {
   unsigned long long* const mine = status + tile;
   if (lane == 0) __hip_atomic_store(mine, (1ull << 62) | tag | (u64)run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1216,7 +1194,6 @@ __device__ __forceinline__ void group_extract_slot(const GroupExtractParams& P, 
 #define PART_AGG_LOOP _Pragma("unroll") for (u32 s = 0; s < kPartNAggs; ++s)
 #define PART_DESC(s) kPartDesc[s]
 #define PART_DENSE(P) (kPartDense != 0u)
-#define PART_SPLIT(P) (kPartSplit != 0u)
 #else
 #define PART_NG(P) (P).n_gaggs
 #define PART_W(P) (P).rec_words
@@ -1225,7 +1202,6 @@ __device__ __forceinline__ void group_extract_slot(const GroupExtractParams& P, 
 #define PART_AGG_LOOP for (u32 s = 0; s < n_aggs; ++s)
 #define PART_DESC(s) readlane64(mydesc, (int)(s))
 #define PART_DENSE(P) ((P).dense.on != 0u)
-#define PART_SPLIT(P) ((P).split != 0u)
 #endif
 #ifndef FKEY   /* (vm_body.inc defines the same for the pipeline kernel's GAGG handlers) */
 #define FKEY(d) ({ u64 b_ = d2u((double)(d)); (b_ & 0x8000000000000000ull) ? ~b_ : (b_ | 0x8000000000000000ull); })
@@ -1233,14 +1209,6 @@ __device__ __forceinline__ void group_extract_slot(const GroupExtractParams& P, 
 /* PART_ROWS: records per lane per step -- a constant of part_agg_body (2; the resident form, at one workgroup per CU, takes RESIDENT_ROWS) */
 #ifndef SSGPU_RESIDENT_ROWS
 #define SSGPU_RESIDENT_ROWS 2   /* (4 and 8 measured the same: the kernel is bound by instruction issue, ~350 VALU instructions per row) */
-#endif
-#ifndef SSGPU_PART_NT
-#define SSGPU_PART_NT 0         /* 1: partition records are read with non-temporal loads (read once; A/B through SSGPU_RTC_FLAGS) */
-#endif
-#if SSGPU_PART_NT
-#define PART_LD(p) __builtin_nontemporal_load(p)
-#else
-#define PART_LD(p) (*(p))
 #endif
 #ifndef SSGPU_PART_ROWS
 #define SSGPU_PART_ROWS 2       /* records per lane per step of the record form (4: measured the same, profiles/r06_part_rows.txt) */
@@ -1451,38 +1419,6 @@ __device__ __forceinline__ void part_agg_body(const PartAggParams& P, const SRC&
         }
     }
   }
-  if constexpr (!PLAIN) {
-    if (P.accumulate && PART_DENSE(P) && !P.slab_segs) {
-      // the table an earlier launch dumped for this partition (same layout as the dump at the end of this function), read back: the
-      // rows of this launch are one more range of the same input
-      __syncthreads();
-      const u32 chunk = part / P.dense.chunk_parts, pin = part - chunk * P.dense.chunk_parts;
-      const u64* const keys_c = reinterpret_cast<const u64*>(reinterpret_cast<const char*>(P.T.keys) + (u64)chunk * P.dense.chunk_stride);
-      const u64* const acc_c = reinterpret_cast<const u64*>(reinterpret_cast<const char*>(P.T.acc) + (u64)chunk * P.dense.chunk_stride);
-      const u32* const cnt_c = reinterpret_cast<const u32*>(reinterpret_cast<const char*>(P.T.cnt) + (u64)chunk * P.dense.chunk_stride);
-      const u64 sp = (u64)P.dense.chunk_slots;
-      const bool special_used = keys_c[sp] != VM_KEY_EMPTY;
-      for (u32 e0 = 0; e0 < C; e0 += SSGPU_PART_THREADS) {
-        const u32 e = e0 + t, ec = e < C ? e : 0u;
-        const u64 packed = ssgpu_dense_key_of(P.dense, ec * P.dense.n_parts + part);   // (uniform loop over the keys: outside the divergent part)
-        if (e < C) {
-          const bool from_special = packed == VM_KEY_EMPTY && special_used;
-          if (from_special) {
-            lkeys[e] = 0ull;
-            for (u32 s = 0; s < ng; ++s) { lacc[(size_t)e * st + s] = acc_c[sp * ng + s]; if (any_cnt) lcnt[(size_t)e * st + s] = cnt_c[sp * ng + s]; }
-          } else if (keys_c[(u64)pin * C + e] != VM_KEY_EMPTY) lkeys[e] = 0ull;
-        }
-      }
-      __syncthreads();
-      for (u32 i = t; i < C * ng; i += SSGPU_PART_THREADS) {
-        const u32 e = i / ng, l = e * st + i % ng;
-        if (lkeys[e] != VM_KEY_EMPTY && !(special_used && ssgpu_dense_key_of(P.dense, e * P.dense.n_parts + part) == VM_KEY_EMPTY)) {
-          lacc[l] = acc_c[(u64)pin * C * ng + i];
-          if (any_cnt) lcnt[l] = cnt_c[(u64)pin * C * ng + i];
-        }
-      }
-    }
-  }
   u32 total = 0;
   if constexpr (!PLAIN) {
     u32 n = t < G ? P.counts[P.slab_segs ? (u64)(seg0 + t) : (u64)part * G + t] : 0u;    // G <= 1024 (the host caps the scatter grid)
@@ -1492,11 +1428,7 @@ __device__ __forceinline__ void part_agg_body(const PartAggParams& P, const SRC&
     if (t == 0) segoff[G] = total;
   }
   __syncthreads();
-  // split records (dense partitions): W - 1 payload words per record in `recs`, the table entry (word 0) in a 16-bit array of its own
-  const bool split = !PLAIN && PART_SPLIT(P);
-  const u32 RW = split ? W - 1u : W;
-  const u64* const recs = PLAIN ? nullptr : P.recs + (P.slab_segs ? (u64)seg0 : (u64)SEG_INDEX(part, 0u, P.n_parts, G)) * P.seg_cap * RW;
-  const unsigned short* const rentry = split ? P.recs_entry + (u64)SEG_INDEX(part, 0u, P.n_parts, G) * P.seg_cap : nullptr;
+  const u64* const recs = PLAIN ? nullptr : P.recs + (P.slab_segs ? (u64)seg0 : (u64)SEG_INDEX(part, 0u, P.n_parts, G)) * P.seg_cap * W;
   const u64 seg_step = PLAIN ? 0ull : P.slab_segs ? (u64)P.seg_cap : (u64)(SEG_INDEX(part, 1u, P.n_parts, G) - SEG_INDEX(part, 0u, P.n_parts, G)) * P.seg_cap;   // records between this partition's consecutive segments
   const u32 seg_cap = P.seg_cap, n_aggs = PART_NAGGS(P);
   const u64 mydesc = (t & 63u) < n_aggs ? P.desc[t & 63u] : 0ull;   // lane s of every wave holds aggregate s's descriptor
@@ -1605,7 +1537,7 @@ __device__ __forceinline__ void part_agg_body(const PartAggParams& P, const SRC&
         while (i >= segoff[seg + 1u]) ++seg;
         const u64* rp = recs + ((u64)seg * seg_step + (i - segoff[seg])) * W;
 #pragma unroll
-        for (int w = 0; w < MAXW; ++w) pre[j][w] = (u32)w < W ? PART_LD(rp + w) : 0ull;
+        for (int w = 0; w < MAXW; ++w) pre[j][w] = (u32)w < W ? rp[w] : 0ull;
       }
     }
     asm volatile("" ::: "memory");     // (the loads stay here: left alone the compiler sinks them to their first use, the top of the next trip)
@@ -1616,19 +1548,9 @@ __device__ __forceinline__ void part_agg_body(const PartAggParams& P, const SRC&
       live[j] = i < total;
       if (live[j]) {
         while (i >= segoff[seg + 1u]) ++seg;              // empty segments are stepped over
-        const u64 ri = (u64)seg * seg_step + (i - segoff[seg]);
-        if (split) {
-          // (RW even -- a specialised build knows it: the payload is 16-byte aligned and leaves as dwordx4 loads)
-          const u64* rp = recs + ri * RW;
-          if (!(RW & 1u)) rp = reinterpret_cast<const u64*>(__builtin_assume_aligned(rp, 16));
-          rec[j][0] = (u64)__builtin_nontemporal_load(rentry + ri);
+        const u64* rp = recs + ((u64)seg * seg_step + (i - segoff[seg])) * W;
 #pragma unroll
-          for (int w = 1; w < MAXW; ++w) rec[j][w] = (u32)w < W ? __builtin_nontemporal_load(rp + (w - 1)) : 0ull;
-        } else {
-        const u64* rp = recs + ri * W;
-#pragma unroll
-        for (int w = 0; w < MAXW; ++w) rec[j][w] = (u32)w < W ? PART_LD(rp + w) : 0ull;
-        }
+        for (int w = 0; w < MAXW; ++w) rec[j][w] = (u32)w < W ? rp[w] : 0ull;
       } else {
 #pragma unroll
         for (int w = 0; w < MAXW; ++w) rec[j][w] = 0ull;
@@ -1651,12 +1573,11 @@ __device__ __forceinline__ void part_agg_body(const PartAggParams& P, const SRC&
     for (int j = 0; j < PART_ROWS; ++j) {
       li[j] = C * st;
       const u64 key = rec[j][0];
-      if (P.debug & 2u) { li[j] = __umulhi(hash_local(key), C) * st; continue; }   // development: no probe
       if (live[j]) {
         if (PART_DENSE(P)) {
           // no probe: the entry IS the index (one table of all slots) or index / partitions; the key word only marks the entry used
           u32 pp;
-          const u32 e = (P.slab_segs || split) ? (u32)key : ssgpu_dense_entry(P.dense, (u32)key, &pp);
+          const u32 e = P.slab_segs ? (u32)key : ssgpu_dense_entry(P.dense, (u32)key, &pp);
           li[j] = e * st;
           lkeys[e] = 0ull;
         } else if (PLAIN && P.hot_only) {
@@ -1692,11 +1613,6 @@ __device__ __forceinline__ void part_agg_body(const PartAggParams& P, const SRC&
     u32 last_off = 0xFFFFFFFFu; u64 val[PART_ROWS];
 #pragma unroll
     for (int j = 0; j < PART_ROWS; ++j) val[j] = 0;
-    if (P.debug & 1u) {   // development: records loaded and probed, nothing aggregated
-#pragma unroll
-      for (int j = 0; j < PART_ROWS; ++j) if (live[j]) LDS_ADD(lacc + li[j], rec[j][1] ^ rec[j][(MAXW - 1) & 4]);
-      continue;
-    }
     PART_AGG_LOOP {
       // the aggregate's descriptor comes out of a register (lane s of `mydesc`): a scalar memory load here would
       // share its wait counter with the LDS atomics in flight and drain them once per aggregate
@@ -2032,30 +1948,6 @@ hipError_t ssgpu_launch_pipeline(const VmParams& P, int K, int grid, hipStream_t
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
-}
-// workgroups of the pipeline kernel one CU can hold at once for this program (registers and LDS): programs whose tiles
-// wait for each other (SEL_RANK_LB) must not launch more workgroups than are resident together
-int ssgpu_pipeline_resident_per_cu(const VmParams& P, int K) {
-  int n = 0;
-  hipError_t e = hipErrorInvalidValue;
-  const size_t lds = P.lds_bytes;
-  if (P.uses_math) {
-    switch (K) {
-      case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ssgpu_pipeline_kernel<1, true>, VM_WG_THREADS, lds); break;
-      case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ssgpu_pipeline_kernel<2, true>, VM_WG_THREADS, lds); break;
-      case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ssgpu_pipeline_kernel<4, true>, VM_WG_THREADS, lds); break;
-      default: break;
-    }
-  } else {
-    switch (K) {
-      case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ssgpu_pipeline_kernel<1, false>, VM_WG_THREADS, lds); break;
-      case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ssgpu_pipeline_kernel<2, false>, VM_WG_THREADS, lds); break;
-      case 4: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ssgpu_pipeline_kernel<4, false>, VM_WG_THREADS, lds); break;
-      default: break;
-    }
-  }
-  if (e != hipSuccess) { (void)hipGetLastError(); return 1; }
-  return n < 1 ? 1 : n;
 }
 // NOT_UNIQUE hash join, expansion: output row o belongs to the lhs row i whose run [offsets[i],
 // offsets[i] + count[i]) contains it (binary search over the exclusive scan of the run counts) and to

@@ -46,8 +46,6 @@ struct ssgpu_ctx {
   // of the C++ facade on a loaded GPU.  Every upload raises the flag; the next run of ANY plan of the context orders its stream behind the copies.
   std::atomic<bool> copy_pending{false};
   hipEvent_t copy_ev = nullptr;
-  hipStream_t side_stream = nullptr;      // created on first use: the aggregation of one row range of a dense GroupAggregate runs here, beside the scatter of the next
-  hipEvent_t side_ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool own_stream = false;
   int cu_count = 0;
   std::string err;
@@ -63,7 +61,6 @@ struct ssgpu_ctx {
   int64_t part_n = 0;            // initial number of hash partitions (0 = 512)
   int64_t part_wgs_per_cu = 0;   // resident workgroups per CU of the scatter pass (0 = wgs_per_cu)
   int64_t part_lds_target = 0;   // LDS target of the scatter pass's tile (0 = lds_target_bytes)
-  int64_t part_agg_debug = 0;
   int64_t sort_records = 1;      // 0: always gather payload columns one by one
   int64_t sort_hybrid = 1;       // 0: never take the high-half-first shortcut for wide keys
   int64_t group_slab = 1;        // 0: never take the slab form of the partitioned GroupAggregate
@@ -81,20 +78,15 @@ struct ssgpu_ctx {
                                  // step a plan without touching the host opt in (distributed.py, sharded.h, bench.py) and keep their input alive.
   int64_t part_prefetch = 1;     // specialised partition aggregation, records of <= 6 words: the loads of trip k + 1 are issued before trip k's LDS atomics
   int64_t fuse_emit = 1;         // ScalarAggregate: the finish launch also emits the result row (0: a launch of its own, as until round 6)
-  int64_t part_overlap_rows = 1 << 23;   // ... inputs of at least this many rows
-  int64_t part_overlap = 1;      // dense partitions over >= 2^23 rows: > 1: the input is taken in this many row ranges, range k aggregated (side stream) while range k + 1 is scattered. Measured slower (the two kernels share the memory system: profiles/r06_overlap_ab.txt): off
   int64_t pscat_pipe = 1;        // specialised plain scatter: the software-pipelined form (tile k + 1 loaded, ranked and reserved while tile k is staged and flushed)
   int64_t pscat_threads = 0, pscat_rows = 0, pscat_wgs = 0;   // launch shape of the plain scatter (0: 1024 threads x 2 rows, one workgroup per CU; ssgpu_part_scatter_plain_geom)
-  int64_t part_split = 0;        // dense partitions: records leave the plain scatter as payload words + 16-bit table entries (0: whole records, index word included)
   int64_t part_plain = 1;        // 0: never run the partition scatter as its own kernel (plain stages), always as the VM program
-  int64_t part_scatter_debug = 0;   // development: 1 = the scatter writes its records sequentially (wrong results)
   int64_t sort_compact = 1;      // 0: never sort (high half << 32 | row id) words instead of (key, row id) pairs
   int64_t sort_hi_digits = 4;    // high digits the hybrid sort passes over before fixing ties: 2..4, 0 = by row count
   int64_t part_agg_lds = 0;      // LDS bytes of phase 2's workgroup (0 = 80 KiB: two workgroups per CU)
   int64_t profile = 1;           // record HIP events around kernels
   int64_t profile_total = 1;     // ... and around the whole run (kernel_ms); 0 keeps only the dominant kernel's pair
   int64_t debug_timing = 0;
-  int64_t part_rec_align = 0;    // partition records padded to a multiple of this many bytes (plans created after the option is set)
   int64_t specialize = 3;        // plans created on this context run kernels specialised for them by runtime compilation (rtc.cpp):
                                  // 1 = yes, compiled when a kernel shape is first launched (the first run; a later run only if run
                                  // feedback moves a GroupAggregate to another execution shape) -- the run WAITS for the compiler;
@@ -105,7 +97,6 @@ struct ssgpu_ctx {
                                  // later processes) pick the kernel up; 0 (and the legacy -1) = only plans that ask for it with
                                  // ssgpu_plan_specialize.
   int64_t specialize_min_rows = 1 << 22;   // option 3: runs over fewer input rows never start a compilation (their kernels take microseconds)
-  bool filter_single_pass = false;   // materialising Filter: one pass with decoupled look-back instead of count pass + scan + store pass (plans created after the option is set)
 };
 
 // Device memory a plan holds, against its soft quota (ssgpu_plan_set_memory_limit = MemoryLimit, memory.h:465): every
@@ -267,10 +258,7 @@ struct StageExec {
   DevBuf wg_partials, slot_recs, slot_kind, emit_descs, state;
   // filter compaction
   DevBuf tile_counts, tile_offsets, total;
-  DevBuf lb_status;             // single-pass form: one look-back word per tile
   DevBuf xstatus; uint64_t x_epoch = 0;   // group extraction (one launch, decoupled look-back): one status word per 512-slot tile, stamped with the run's epoch
-  uint64_t lb_epoch = 0;        // stamp of the single-pass compaction status words (run_materialize)
-  int lb_resident_per_cu = 0;   // workgroups of this stage's program a CU holds at once (occupancy API)
   // group table
   DevBuf gkeys, gacc, gcnt, goverflow, gpattern, gmergeop;
   int group_wgs = 3;            // resident workgroups per CU of the group stage (adapted from run feedback)
@@ -333,8 +321,6 @@ struct StageExec {
   bool emit_ready = false;
   bool emitted_with_finish = false;  // this run's finish launch also emitted the result row
   bool pattern_ready = false;
-  int last_row_ranges = 1;           // row ranges the last dense-partition run took its input in (scatter of one beside the aggregation of the one before)
-  bool last_split_records = false;   // the last partitioned run wrote split records (payload + 16-bit entries)
   // outputs
   DevBuf out_arena;          // large results: ONE allocation, `out` holds views into it (ensure_out_cols)
   std::vector<OutCol> out;
@@ -500,9 +486,7 @@ static void ctx_release(ssgpu_ctx* c) {
   if (c->device >= 0) {
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->copy_ev) { (void)hipEventDestroy(c->copy_ev); c->copy_ev = nullptr; }
-    for (hipEvent_t& e : c->side_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (g_device_contexts.fetch_sub(1) == 1) (void)g_pool.trim(-1);   // nobody is left to take a parked block
   }
   delete c;
@@ -547,7 +531,6 @@ int ssgpu_ctx_set_option(ssgpu_ctx* c, const char* key, int64_t value) {
   else if (k == "part_wgs_per_cu") c->part_wgs_per_cu = value;
   else if (k == "part_lds_target") c->part_lds_target = value;
   else if (k == "part_agg_lds") c->part_agg_lds = value;
-  else if (k == "part_agg_debug") c->part_agg_debug = value;
   else if (k == "group_slab") c->group_slab = value;
   else if (k == "group_resident") c->group_resident = value;
   else if (k == "group_dense") c->group_dense = value;
@@ -556,18 +539,14 @@ int ssgpu_ctx_set_option(ssgpu_ctx* c, const char* key, int64_t value) {
   else if (k == "group_scout") c->group_scout = value;
   else if (k == "group_scout_rows") c->group_scout_rows = value;
   else if (k == "part_plain") c->part_plain = value;
-  else if (k == "part_split") c->part_split = value;
   else if (k == "pscat_threads") c->pscat_threads = value;
   else if (k == "pscat_rows") c->pscat_rows = value;
   else if (k == "pscat_wgs") c->pscat_wgs = value;
   else if (k == "pscat_pipe") c->pscat_pipe = value;
-  else if (k == "part_overlap") c->part_overlap = value;
   else if (k == "fuse_emit") c->fuse_emit = value;
   else if (k == "part_prefetch") c->part_prefetch = value;
-  else if (k == "part_overlap_rows") c->part_overlap_rows = value;
   else if (k == "lazy_feedback") c->lazy_feedback = value;
   else if (k == "async_handoff") c->async_handoff = value;
-  else if (k == "part_scatter_debug") c->part_scatter_debug = value;
   else if (k == "sort_records") c->sort_records = value;
   else if (k == "sort_hybrid") c->sort_hybrid = value;
   else if (k == "sort_hi_digits") c->sort_hi_digits = value;
@@ -578,10 +557,8 @@ int ssgpu_ctx_set_option(ssgpu_ctx* c, const char* key, int64_t value) {
   } else if (k == "profile") c->profile = value;
   else if (k == "profile_total") c->profile_total = value;
   else if (k == "debug_timing") c->debug_timing = value;
-  else if (k == "filter_single_pass") c->filter_single_pass = value != 0;
   else if (k == "specialize") c->specialize = value;
   else if (k == "specialize_min_rows") c->specialize_min_rows = value < 0 ? 0 : value;
-  else if (k == "part_rec_align") c->part_rec_align = value;
   else { c->err = "unknown option " + k; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
   return SSGPU_OK;
 }
@@ -806,8 +783,6 @@ int ssgpu_plan_create(ssgpu_ctx* c, const ssgpu_plan_desc* d, ssgpu_plan** out) 
 }
 static int plan_finish_create(ssgpu_ctx* c, ssgpu_plan* p, Status s, ssgpu_plan** out) {
   p->ctx = c;
-  p->desc.filter_single_pass = c->filter_single_pass;
-  p->desc.part_rec_align = (int)c->part_rec_align;
   if (s.ok()) s = lower_plan(p->desc, &p->stages, &p->result_schema, &p->describe);
   if (!s.ok()) { delete p; return fail(c, s); }
   for (auto& st : p->stages) {
@@ -1123,12 +1098,10 @@ int grid_for(ssgpu_ctx* c, const ProgramLayout& L, int n_tiles) {
   return (int)std::max<int64_t>(g, 1);
 }
 
-// the stage's main program: its specialised kernel when the plan runs specialised kernels, else the interpreter.  (The
-// single-pass Filter keeps the interpreter: its grid is sized from THAT kernel's residency -- every workgroup must be
-// resident for the look-back to make progress -- and a specialised build may hold fewer per CU.)
+// the stage's main program: its specialised kernel when the plan runs specialised kernels, else the interpreter
 static hipError_t launch_main(ssgpu_plan* p, const Stage& st, StageExec& ex, const VmParams& P, int K, int grid) {
   ssgpu_ctx* c = p->ctx;
-  if (p->specialize && !P.debug_pc && !st.single_pass) {
+  if (p->specialize && !P.debug_pc) {
     void* h = rtc_for(p, ex, ex.rtc_main, st.main, ex.lay, ex.host_prog_main, ex.n_instr_main, P.lds_bytes, "");
     if (h) return ssgpu_launch_pipeline_rtc(h, P, grid, ex.rtc_main.static_lds != 0, c->stream);
   }
@@ -1450,16 +1423,11 @@ int run_materialize(ssgpu_plan* p, size_t si, const InCols& in0, int64_t row_id_
   }
   rc = attach_pc_profile(c, ex, &P);
   if (rc != SSGPU_OK) return rc;
-  int grid = grid_for(c, ex.lay, P.n_tiles);
-  if (st.single_pass) {
-    // tiles wait for the counts of earlier tiles: every workgroup of the grid has to be resident at once
-    if (ex.lb_resident_per_cu == 0) ex.lb_resident_per_cu = ssgpu_pipeline_resident_per_cu(P, ex.lay.K);
-    grid = std::max(1, std::min(grid, c->cu_count * ex.lb_resident_per_cu));
-  }
+  const int grid = grid_for(c, ex.lay, P.n_tiles);
   ex.grid = grid;
   p->counters.tile_rows = P.tile_rows; p->counters.grid = grid; p->counters.lds_bytes = (int32_t)ex.lay.lds_bytes;
   bool dom0_recorded = false;
-  if (st.has_filter && !st.single_pass) {
+  if (st.has_filter) {
     const int nt = std::max(P.n_tiles, 1);
     HIP_TRY(c, ex.tile_counts.ensure((size_t)nt * sizeof(uint32_t)));
     HIP_TRY(c, ex.tile_offsets.ensure((size_t)nt * sizeof(uint32_t)));
@@ -1478,25 +1446,6 @@ int run_materialize(ssgpu_plan* p, size_t si, const InCols& in0, int64_t row_id_
                                         ex.total.as<uint64_t>(), c->stream));
     P.tile_offsets = ex.tile_offsets.as<unsigned int>();
     p->counters.n_launches += 2;
-    ex.out_rows = -1;
-  } else if (st.has_filter) {
-    // single pass: tiles are ranked by decoupled look-back over lb_status (one word per
-    // tile, stamped with this run's epoch: words of earlier runs read as "not yet", so the buffer is zeroed only when
-    // it is (re)allocated or the 30-bit epoch wraps); ex.total = [survivors u64][ticket u32][gave-up flag u32]
-    const size_t nt = (size_t)std::max(P.n_tiles, 1);
-    const size_t had = ex.lb_status.cap;
-    HIP_TRY(c, ex.lb_status.ensure(nt * sizeof(uint64_t)));
-    ex.lb_epoch = (ex.lb_epoch + 1) & 0x3FFFFFFFull;
-    if (ex.lb_status.cap != had || ex.lb_epoch == 0) {
-      HIP_TRY(c, hipMemsetAsync(ex.lb_status.p, 0, ex.lb_status.cap, c->stream));
-      if (ex.lb_epoch == 0) ex.lb_epoch = 1;
-    }
-    HIP_TRY(c, ex.total.ensure(16));
-    HIP_TRY(c, hipMemsetAsync(ex.total.p, 0, 16, c->stream));
-    P.lb_status = ex.lb_status.as<unsigned long long>();
-    P.lb_ctrl = ex.total.as<unsigned int>();
-    P.lb_epoch = ex.lb_epoch;
-    p->counters.n_launches += 1;
     ex.out_rows = -1;
   } else if (in.rows_dev) {
     ex.out_rows = -1; ex.out_rows_dev = in.rows_dev;   // as many rows as came in: the same device word
@@ -1847,29 +1796,23 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
     ex.last_plain_scatter = plain;
     // records a (partition, workgroup) segment holds: the expected share of the INPUT rows (an upper bound of the
     // selected ones) with head room for the spread of a uniform hash, times the growth factor of earlier overflows
-    // Row ranges (dense partitions of a large input): the scatter is bound by memory and latency, the aggregation by LDS atomics, and
-    // each needs about half a CU's LDS -- so the input is taken in KR ranges, and while range k + 1 is scattered (this stream) range k
-    // is aggregated (side stream) into the same tables, each launch starting from what the one before it dumped (PartAggParams::accumulate).
-    // Every range has its own segments; `range_rows` is what the segments are sized for.
-    const uint32_t KR = (dense && plain && !resident && !slab && c->part_split == 0 && c->part_overlap > 1 && in.rows >= std::max<int64_t>(c->part_overlap_rows, 1)) ? (uint32_t)std::min<int64_t>(c->part_overlap, 8) : 1u;
-    const int64_t range_rows = (in.rows + KR - 1) / KR;
-    const double expect = (double)std::max<int64_t>(range_rows, 1) / ((double)NP * (double)grid);
+    const double expect = (double)std::max<int64_t>(in.rows, 1) / ((double)NP * (double)grid);
     uint64_t seg_cap = (uint64_t)((expect * 1.25 + 8.0 * std::sqrt(expect) + 32.0) * (double)ex.part_seg_growth);
     if (plain) {
       // the plain scatter deals tiles of 2048 (1024) rows round-robin to one workgroup per CU, and a workgroup appends to the segments of
       // ITS XCD: with few tiles the XCDs' shares differ by whole tiles (one tile: every row in XCD 0's segments)
       const PscatGeom geom = ssgpu_part_scatter_plain_geom(NP, W0, (int)c->pscat_threads, (int)c->pscat_rows, (int)c->pscat_wgs);
       const uint64_t T = (uint64_t)geom.threads * geom.rows;
-      const uint64_t tiles = ((uint64_t)std::max<int64_t>(range_rows, 1) + T - 1) / T;
-      const uint64_t pg = (uint64_t)std::min<int64_t>(std::max(c->cu_count, 1), std::max<int64_t>(1, (range_rows + 1023) / 1024));
+      const uint64_t tiles = ((uint64_t)std::max<int64_t>(in.rows, 1) + T - 1) / T;
+      const uint64_t pg = (uint64_t)std::min<int64_t>(std::max(c->cu_count, 1), std::max<int64_t>(1, (in.rows + 1023) / 1024));
       const uint64_t xcds = std::min<uint64_t>(std::min<uint64_t>(SSGPU_PSCAT_XCDS, pg), tiles);
-      const double per_xcd = (double)std::min<uint64_t>((uint64_t)std::max<int64_t>(range_rows, 1), (tiles + xcds - 1) / xcds * T);
+      const double per_xcd = (double)std::min<uint64_t>((uint64_t)std::max<int64_t>(in.rows, 1), (tiles + xcds - 1) / xcds * T);
       const double expect_x = per_xcd / (double)NP;
       seg_cap = (uint64_t)((expect_x * 1.3 + 8.0 * std::sqrt(expect_x) + 64.0) * (double)ex.part_seg_growth);   // (partitions differ by their group counts, too)
     }
     if (slab) seg_cap = (uint64_t)((Ps.n_tiles + grid - 1) / grid) * (uint64_t)Ps.tile_rows;   // all rows a workgroup can see: never full
     if (resident) seg_cap = 1;                                                      // (no records are written)
-    const uint64_t n_segs = resident ? 1ull : (uint64_t)NP * (uint64_t)grid;     // (of ONE row range)
+    const uint64_t n_segs = resident ? 1ull : (uint64_t)NP * (uint64_t)grid;
     if (n_segs * seg_cap >= 0xFFFFFFFFull) { *fallback = true; return SSGPU_OK; }   // record indices are 32-bit
     unsigned long long* tkeys; unsigned long long* tacc; unsigned int* tcnt;   // the global table of this run
     DenseKeyMap dmap; memset(&dmap, 0, sizeof(dmap));
@@ -1885,14 +1828,8 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
       HIP_TRY(c, ex.gcnt.ensure(slots * ng * 4));
       tkeys = ex.gkeys.as<unsigned long long>(); tacc = ex.gacc.as<unsigned long long>(); tcnt = ex.gcnt.as<unsigned int>();
     }
-    // split records: a dense partition's record needs no key -- its table entry (index / partitions < 2^16) travels in a 16-bit array
-    // next to the payload words: 34 bytes per row written and read back where a whole record with its index word took 40
-    const bool split = dense && plain && !resident && c->part_split != 0 && W0 >= 2u && C <= 65536u;
-    const size_t payload_bytes = split ? ((n_segs * seg_cap * (size_t)(W0 - 1u) * 8 + 255) & ~(size_t)255) : n_segs * seg_cap * (size_t)st.part_rec_bytes;
-    const size_t range_rec_bytes = (payload_bytes + 255) & ~(size_t)255;     // (KR > 1 implies whole records: one range's segments)
-    if (ex.part_recs.ensure((KR > 1 ? range_rec_bytes * KR : payload_bytes + (split ? n_segs * seg_cap * 2 : 0)) + 16) != hipSuccess) { (void)hipGetLastError(); *fallback = true; return SSGPU_OK; }
-    ex.last_split_records = split; ex.last_row_ranges = (int)KR;
-    HIP_TRY(c, ex.part_hist.ensure(n_segs * KR * 4));
+    if (ex.part_recs.ensure(n_segs * seg_cap * (size_t)st.part_rec_bytes + 16) != hipSuccess) { (void)hipGetLastError(); *fallback = true; return SSGPU_OK; }
+    HIP_TRY(c, ex.part_hist.ensure(n_segs * 4));
     {
       GroupInitParams I; memset(&I, 0, sizeof(I));
       I.pattern = ex.gpattern.as<unsigned long long>(); I.ng = ng;
@@ -1912,14 +1849,13 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
       }
       I.z[0] = ex.goverflow.as<unsigned int>(); I.nz[0] = 4;
       I.z[1] = ex.error_flag.as<unsigned int>(); I.nz[1] = 1;
-      if (plain) { I.z[2] = ex.part_hist.as<unsigned int>(); I.nz[2] = n_segs * KR; }     // the plain scatter's segment counters
+      if (plain) { I.z[2] = ex.part_hist.as<unsigned int>(); I.nz[2] = n_segs; }     // the plain scatter's segment counters
       I.z[3] = ex.total.as<unsigned int>(); I.nz[3] = 4;                             // the extraction's row count, ticket and gave-up flag
       HIP_TRY(c, ssgpu_launch_group_init(I, c->stream));
     }
     Ps.error_flag = ex.error_flag.as<unsigned int>();
     Ps.tile_counts = ex.part_hist.as<unsigned int>();
     Ps.part_seg_cap = (uint32_t)seg_cap;
-    Ps.part_pad = (uint32_t)c->part_scatter_debug;
     Ps.part_overflow = ex.goverflow.as<unsigned int>() + 1;
     Ps.outputs[0].dst = ex.part_recs.p; Ps.outputs[0].width = st.part_rec_bytes;
     if (!plain && !resident) { int rc = attach_pc_profile(c, ex, &Ps); if (rc != SSGPU_OK) return rc; }
@@ -1959,7 +1895,6 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
       else HIP_TRY(c, ssgpu_launch_group_resident(H, S, hot_lds, hgrid, c->stream));
       p->counters.n_launches += 1;
     }
-    std::function<int(uint32_t)> scatter_range;
     if (resident) {
       // nothing to scatter
     } else if (plain) {
@@ -1968,7 +1903,6 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
       S.dense = dmap;
       S.n_parts = NP; S.seg_cap = (uint32_t)seg_cap; S.rec_words = W0; S.rec_inv = (uint32_t)(0x100000000ull / W0 + 1ull);
       S.recs = ex.part_recs.as<unsigned long long>(); S.counts = ex.part_hist.as<unsigned int>(); S.overflow = ex.goverflow.as<unsigned int>() + 1;
-      if (split) { S.split = 1u; S.recs_entry = reinterpret_cast<unsigned short*>(ex.part_recs.as<char>() + payload_bytes); S.pay_inv = W0 > 2u ? (uint32_t)(0x100000000ull / (W0 - 1u) + 1ull) : 0u; }
       // one fat workgroup per CU: every workgroup more multiplies the open lines and the per-tile atomics
       PscatGeom geom = ssgpu_part_scatter_plain_geom(NP, W0, (int)c->pscat_threads, (int)c->pscat_rows, (int)c->pscat_wgs);
       // (the pipelined form -- specialised builds -- keeps a second array of per-partition counters behind the staging area)
@@ -1979,7 +1913,7 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
       void* hs = nullptr;
       if (p->specialize) {
         const uint32_t lds = geom.lds;
-        const uint32_t tag = NP * 128u + (geom.pipe ? 64u : 0u) + (geom.threads == 512u ? 32u : 0u) + geom.rows * 4u + (split ? 2u : 0u) + (dense ? 1u : 0u);
+        const uint32_t tag = NP * 128u + (geom.pipe ? 64u : 0u) + (geom.threads == 512u ? 32u : 0u) + geom.rows * 4u + (dense ? 1u : 0u);
         if (!(ex.rtc_plain.tried && ex.rtc_plain.static_lds == lds && ex.rtc_plain.tag == tag && !ex.rtc_plain.ask_again() && !ex.rtc_plain.stronger_mode_now())) {
           if (ex.rtc_plain.h) { HIP_TRY(c, hipStreamSynchronize(c->stream)); ex.rtc_plain.drop(); }
           ex.rtc_plain.tried = true; ex.rtc_plain.static_lds = lds; ex.rtc_plain.tag = tag;
@@ -1990,25 +1924,9 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
         }
         hs = ex.rtc_plain.h;
       }
-      // range k of the input: the same descriptors over the rows [k * range_rows, ...), into range k's segments
-      scatter_range = [&, S, geom, pgrid, hs](uint32_t k) -> int {
-        PlainScatterParams R = S;
-        if (KR > 1) {
-          const uint64_t lo = (uint64_t)k * (uint64_t)range_rows;
-          R.n_rows = (unsigned long long)std::max<int64_t>(0, std::min<int64_t>(range_rows, in.rows - (int64_t)lo));
-          auto pred_width = [](uint32_t kind) { return kind == 6u ? 1u : (kind == 0u || kind == 1u || kind == 4u) ? 4u : 8u; };
-          for (uint32_t i = 0; i < R.n_keys; ++i) { R.keys[i].data = static_cast<const char*>(R.keys[i].data) + lo * R.keys[i].width; if (R.keys[i].nulls) R.keys[i].nulls += lo; }
-          for (uint32_t i = 0; i < R.n_fields; ++i) if (R.fields[i].src) R.fields[i].src = static_cast<const char*>(R.fields[i].src) + lo * R.fields[i].width;
-          for (uint32_t i = 0; i < R.n_preds; ++i) { R.preds[i].data = static_cast<const char*>(R.preds[i].data) + lo * pred_width(R.preds[i].kind); if (R.preds[i].nulls) R.preds[i].nulls += lo; }
-          R.recs = reinterpret_cast<unsigned long long*>(ex.part_recs.as<char>() + (size_t)k * range_rec_bytes);
-          R.counts = ex.part_hist.as<unsigned int>() + (size_t)k * n_segs;
-        }
-        const int g = (int)std::min<int64_t>(pgrid, std::max<int64_t>(1, ((int64_t)R.n_rows + 1023) / 1024));
-        if (hs) HIP_TRY(c, ssgpu_launch_part_scatter_plain_rtc(hs, R, geom, g, c->stream));
-        else HIP_TRY(c, ssgpu_launch_part_scatter_plain(R, geom, g, c->stream));
-        return SSGPU_OK;
-      };
-      if (KR == 1) { const int rc = scatter_range(0); if (rc != SSGPU_OK) return rc; }
+      const int g = (int)std::min<int64_t>(pgrid, std::max<int64_t>(1, ((int64_t)S.n_rows + 1023) / 1024));
+      if (hs) HIP_TRY(c, ssgpu_launch_part_scatter_plain_rtc(hs, S, geom, g, c->stream));
+      else HIP_TRY(c, ssgpu_launch_part_scatter_plain(S, geom, g, c->stream));
       (void)scatter_grid;
     } else {
       void* h = Ps.debug_pc ? nullptr : rtc_for(p, ex, ex.rtc_pscatter, st.part_scatter, ex.lay_pscatter, ex.host_prog_pscatter, ex.n_instr_pscatter, Ps.lds_bytes, "partition scatter: ");
@@ -2019,7 +1937,6 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
     PartAggParams A;
     memset(&A, 0, sizeof(A));
     A.recs = ex.part_recs.as<unsigned long long>();
-    if (split) { A.split = 1u; A.recs_entry = reinterpret_cast<const unsigned short*>(ex.part_recs.as<char>() + payload_bytes); }
     A.counts = ex.part_hist.as<unsigned int>();
     A.n_segs = (unsigned int)grid; A.seg_cap = (unsigned int)seg_cap; A.rec_words = W; A.n_parts = NP;
     if (slab) {   // one aggregation workgroup per CU, each over a run of the scatter workgroups' segments
@@ -2027,7 +1944,6 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
       A.slab_segs = ((unsigned int)grid + wgs - 1u) / wgs;
       A.n_parts = ((unsigned int)grid + A.slab_segs - 1u) / A.slab_segs;
     }
-    A.debug = (unsigned int)c->part_agg_debug;
     A.local_capacity = C; A.n_gaggs = ng; A.n_aggs = (unsigned int)st.part_aggs.size(); A.any_cnt = any_cnt ? 1u : 0u;
     A.T.keys = tkeys; A.T.acc = tacc; A.T.cnt = tcnt;
     A.dense = dmap;
@@ -2058,39 +1974,18 @@ int run_group_agg_partitioned(ssgpu_plan* p, size_t si, const InCols& in, int64_
       if (p->specialize && ex.rtc_resident.h && ex.rtc_resident.static_lds == agg_lds) HIP_TRY(c, ssgpu_launch_group_resident_rtc(ex.rtc_resident.h, A, S, rgrid, c->stream));
       else HIP_TRY(c, ssgpu_launch_group_resident(A, S, agg_lds, rgrid, c->stream));
     } else
-    if (p->specialize && !(ex.rtc_part.tried && ex.rtc_part.static_lds == agg_lds && ex.rtc_part.tag == (dense ? 1u : 0u) + (split ? 2u : 0u) + (c->part_prefetch ? 4u : 0u) && !ex.rtc_part.ask_again() && !ex.rtc_part.stronger_mode_now())) {
+    if (p->specialize && !(ex.rtc_part.tried && ex.rtc_part.static_lds == agg_lds && ex.rtc_part.tag == (dense ? 1u : 0u) + (c->part_prefetch ? 4u : 0u) && !ex.rtc_part.ask_again() && !ex.rtc_part.stronger_mode_now())) {
       // one kernel per LDS size (hash partitions and the slab form differ in it): compiled when that shape is first run
       if (ex.rtc_part.h) { HIP_TRY(c, hipStreamSynchronize(c->stream)); ex.rtc_part.drop(); }
-      ex.rtc_part.tried = true; ex.rtc_part.static_lds = agg_lds; ex.rtc_part.tag = (dense ? 1u : 0u) + (split ? 2u : 0u) + (c->part_prefetch ? 4u : 0u);
+      ex.rtc_part.tried = true; ex.rtc_part.static_lds = agg_lds; ex.rtc_part.tag = (dense ? 1u : 0u) + (c->part_prefetch ? 4u : 0u);
       std::string why;
-      ex.rtc_part.h = ssgpu_rtc_specialize_part_agg(c->device, A.desc, (int)A.n_aggs, W, ng, any_cnt, agg_lds, &why, nullptr, dense, split, c->part_prefetch != 0);
+      ex.rtc_part.h = ssgpu_rtc_specialize_part_agg(c->device, A.desc, (int)A.n_aggs, W, ng, any_cnt, agg_lds, &why, nullptr, dense, c->part_prefetch != 0);
       ex.rtc_part.asked();
       if (!ex.rtc_part.h && ex.rtc_why.empty()) ex.rtc_why = "partition aggregation: " + why;
     }
-    auto agg_launch = [&](const PartAggParams& AA, hipStream_t on) -> int {
-      if (p->specialize && ex.rtc_part.h && ex.rtc_part.static_lds == agg_lds) HIP_TRY(c, ssgpu_launch_part_agg_rtc(ex.rtc_part.h, AA, on));
-      else HIP_TRY(c, ssgpu_launch_part_agg(AA, agg_lds, on));
-      return SSGPU_OK;
-    };
     if (resident) { /* launched above */ }
-    else if (KR > 1) {
-      if (!c->side_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-      for (uint32_t k = 0; k <= KR; ++k) if (!c->side_ev[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->side_ev[k], hipEventDisableTiming));
-      for (uint32_t k = 0; k < KR; ++k) {
-        { const int rc = scatter_range(k); if (rc != SSGPU_OK) return rc; }
-        HIP_TRY(c, hipEventRecord(c->side_ev[k], c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->side_stream, c->side_ev[k], 0));
-        PartAggParams AK = A;
-        AK.recs = reinterpret_cast<const unsigned long long*>(ex.part_recs.as<char>() + (size_t)k * range_rec_bytes);
-        AK.counts = ex.part_hist.as<unsigned int>() + (size_t)k * n_segs;
-        AK.accumulate = k ? 1u : 0u;
-        { const int rc = agg_launch(AK, c->side_stream); if (rc != SSGPU_OK) return rc; }
-      }
-      HIP_TRY(c, hipEventRecord(c->side_ev[KR], c->side_stream));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, c->side_ev[KR], 0));     // (the extraction, and whatever the caller queues next, follow the last aggregation)
-      p->counters.n_launches += 2 * (KR - 1);
-    }
-    else { const int rc = agg_launch(A, c->stream); if (rc != SSGPU_OK) return rc; }
+    else if (p->specialize && ex.rtc_part.h && ex.rtc_part.static_lds == agg_lds) HIP_TRY(c, ssgpu_launch_part_agg_rtc(ex.rtc_part.h, A, c->stream));
+    else HIP_TRY(c, ssgpu_launch_part_agg(A, agg_lds, c->stream));
     if (c->profile) HIP_TRY(c, hipEventRecord(p->ev_dom1, c->stream));
     p->counters.n_launches += 6;
     p->counters.tile_rows = Ps.tile_rows; p->counters.grid = grid; p->counters.lds_bytes = (int32_t)Ps.lds_bytes;
@@ -2873,7 +2768,7 @@ int check_error_flags(ssgpu_plan* p) {
     f &= 0xFFu;
   }
   for (uint32_t f : flags) {
-    if (f == 3) { c->err = "single-pass compaction: a tile waited for an earlier tile's row count for too long and gave up"; return SSGPU_ERROR_HIP; }
+    if (f == 3) { c->err = "decoupled look-back: a tile waited for an earlier tile's row count for too long and gave up"; return SSGPU_ERROR_HIP; }
     if (f) {
       c->err = f == 2 ? "Evaluation error: invalid argument of a signaling math expression (negative input of SQRT)"
                       : "Evaluation error: division by zero in a signaling expression";
@@ -3192,7 +3087,7 @@ int ssgpu_plan_specialize(ssgpu_plan* p) {
     const int rc = prepare_stage(p, si);
     if (rc != SSGPU_OK) return rc;
     Stage& st = p->stages[si]; StageExec& ex = p->exec[si];
-    if (st.main.empty() || st.single_pass || st.kind == STAGE_GROUP_AGG) continue;
+    if (st.main.empty() || st.kind == STAGE_GROUP_AGG) continue;
     (void)rtc_for(p, ex, ex.rtc_main, st.main, ex.lay, ex.host_prog_main, ex.n_instr_main, ex.lay.lds_bytes, "");
   }
   return SSGPU_OK;
@@ -3210,8 +3105,6 @@ int ssgpu_plan_stage_info(const ssgpu_plan* p, int32_t stage, ssgpu_stage_info* 
   out->plain_scatter = ex.last_plain_scatter ? 1 : 0;
   out->hot_keys = (int32_t)ex.hot_n;
   out->dense_slots = ex.dense.on ? (int32_t)ex.dense.slots : 0;
-  out->split_records = (ex.dense.on && ex.last_group_shape == 1 && ex.last_split_records) ? 1 : 0;
-  out->row_ranges = (ex.dense.on && ex.last_group_shape == 1) ? ex.last_row_ranges : 1;
   return SSGPU_OK;
 }
 void ssgpu_specialized_kernels_trim(int32_t keep) { ssgpu_rtc_trim(keep); }

@@ -126,13 +126,6 @@ enum { VM_MATH_EXP = 1, VM_MATH_LN, VM_MATH_LOG10, VM_MATH_LOG2, VM_MATH_SIN, VM
   X(STORE_8) X(STORE_32) X(STORE_64)     /* dst = out col, a = reg, rows 1:1 */\
   X(STOREC_8) X(STOREC_32) X(STOREC_64)  /* + b = rank reg, c = sel (compact)*/\
   X(STORE_ROWID) /* dst = out col: int64 global row id of survivors, b,c */    \
-  /* single-pass compaction (decoupled look-back over the strided tiles, VmParams.lb_*):                         */\
-  /* SEL_RANK_LB: a = sel -> dst = u32 reg: tile row of the tile's i-th survivor; publishes the tile's count,    */\
-  /* resolves the rows kept by all earlier tiles (scratch words 32/33 = first output row / survivors)            */\
-  /* STOREG_*: dst = out col, a = value, b = the SEL_RANK_LB register: survivors gathered from LDS, lanes on     */\
-  /* consecutive output rows (coalesced, line-aligned stores)                                                    */\
-  X(SEL_RANK_LB) X(STOREG_8) X(STOREG_32) X(STOREG_64)                         \
-  X(BARRIER)     /* workgroup barrier: registers written so far may be read by other threads (STOREG) */ \
   /* PART_RANK: a = key(64), c = sel -> dst = u32 position of the row in the tile's partition-sorted order,    */\
   /* VM_NONE for unselected rows; PART_REC_*: a (, d) = value reg(s), b = position reg, imm = byte offset      */\
   /* inside the record | record bytes << 16 (AoS records in the LDS staging area); PART_FLUSH: imm = record    */\
@@ -262,12 +255,8 @@ struct VmParams {
   uint32_t part_n;              /* PART_RANK: number of hash partitions */
   uint32_t part_lds_off;        /* LDS offset of part_n u32 counters */
   uint32_t part_seg_cap;        /* PART_RANK: records a (partition, workgroup) segment holds */
-  uint32_t part_pad;
   unsigned int* part_overflow;  /* PART_RANK: set to 1 when a segment was full (the host reruns with larger segments) */
   const unsigned int* tile_offsets;
-  unsigned long long* lb_status;  /* SEL_RANK_LB: one word per tile: state << 62 | epoch << 32 | rows (0 = not yet) */
-  unsigned int* lb_ctrl;          /* [0..1] u64 total survivors, [3] look-back gave up                              */
-  unsigned long long lb_epoch;    /* run stamp of lb_status words (stale words of earlier runs read as "not yet")    */
   const unsigned long long* n_rows_dev;  /* optional: the input's row count lives on the DEVICE (a stage fed by a stage whose row count no host has read yet); n_rows / n_tiles are then upper bounds */
   unsigned int* error_flag;     /* low byte != 0: evaluation error (signaling ops); SSGPU_FLAG_NAN_IN_MINMAX: see below */
   unsigned long long* debug;    /* optional [grid][4]: total cycles, barrier-wait cycles, tiles */
@@ -280,6 +269,7 @@ struct VmParams {
   VmStagedCol staged[VM_MAX_STAGED];
   VmOutCol outputs[VM_MAX_OUTPUTS];
 };
+static_assert(sizeof(VmParams) <= 4096, "VmParams must fit the 4 KiB kernel-argument block");
 
 #define VM_FLAG_XCD_CHUNKS 1u
 

@@ -421,43 +421,6 @@
           }
           WG_BARRIER();
         } break;
-        case VM_SEL_RANK_LB: { CASE_FENCE;
-          // single-pass compaction.  (1) count the tile's survivors; (2) publish the count and look back over the
-          // earlier tiles' words for the number of rows they keep; (3) dst[i] = tile row of survivor i.
-          // Tiles are strided over the persistent workgroups, so the tiles one iteration works on are a contiguous window
-          // whose counts appear together; a tile only waits for tiles of the same or the previous iteration, which
-          // belong to workgroups that are resident (the host sizes the grid by the occupancy API for these programs).
-          u32* scratch = reinterpret_cast<u32*>(smem + P.scratch_lds_off);
-          _Pragma("unroll") FOR_PAIRS {
-            Valid2 m = valid_pair_(p, tile_valid, VM_NONE, I.a);
-            u32 c = (u32)__popcll(__ballot(m.x)) + (u32)__popcll(__ballot(m.y));
-            if (lane == 0) scratch[k * VM_WAVES + wave] = c;
-          }
-          WG_BARRIER();
-          u32 run = 0;
-          {
-            const u64 lt = (1ull << lane) - 1ull;
-            u32* inv = reinterpret_cast<u32*>(smem + I.dst);
-            _Pragma("unroll") FOR_PAIRS {
-              u32 mine = run;
-              for (int w = 0; w < wave; ++w) mine += scratch[k * VM_WAVES + w];
-              for (int w = 0; w < VM_WAVES; ++w) run += scratch[k * VM_WAVES + w];
-              Valid2 m = valid_pair_(p, tile_valid, VM_NONE, I.a);
-              const u64 b0 = __ballot(m.x), b1 = __ballot(m.y);
-              const u32 r0 = mine + (u32)__popcll(b0 & lt) + (u32)__popcll(b1 & lt);
-              if (m.x) inv[r0] = 2u * (u32)p;
-              if (m.y) inv[r0 + (m.x ? 1u : 0u)] = 2u * (u32)p + 1u;
-            }
-          }
-          if (wave == 0) {
-            const u32 excl = lookback_rows_before(P.lb_status, tile, run, (P.lb_epoch & 0x3FFFFFFFull) << 32, P.lb_ctrl, P.error_flag, lane);
-            if (lane == 0) {
-              scratch[40] = excl; scratch[41] = run;
-              if (tile == vm_n_tiles - 1) *reinterpret_cast<u64*>(P.lb_ctrl) = (u64)excl + run;
-            }
-          }
-          WG_BARRIER();
-        } break;
         // ---- HashJoin probe + gathers (see VmJoin in vm.h) -------------------------------------
         case VM_JOIN_PROBE: { CASE_FENCE;
           // d = selection (unselected rows are not probed), b = any-NULL flag of the key (a NULL key matches nothing).
@@ -664,27 +627,8 @@
             const bool in1 = w1 < words;
             const u32 g0 = grec[j0], g1 = in1 ? grec[j1] : VM_NONE;
             const u64 v0 = stage[w0], v1 = in1 ? stage[w1] : 0ull;
-            if (P.part_pad == 1u) {   // development (ctx option part_scatter_debug): the same bytes written sequentially -- how much
-              const u64 seq = (u64)tile * (u32)(VM_TILE_UNIT * K) * wpr;   // of the pass is the scatter?  (3.08 -> 1.45 ms)
-              if (g0 != VM_NONE) out[seq + w0] = v0;
-              if (g1 != VM_NONE) out[seq + w1] = v1;
-              continue;
-            }
-            if (P.part_pad >= 2u) {   // development: runs of 2^part_pad records contiguous, the runs scattered (what a per-tile sort by
-              const u32 R = 1u << P.part_pad;   // partition would write with tile_rows / partitions = R): wrong results, right traffic
-              const u64 nruns = ((u64)gridDim.x * NP * P.part_seg_cap) / R;
-              const u64 r0 = ((u64)tile * 2654435761ull + (u64)(j0 / R) * 40503ull) % nruns, r1 = ((u64)tile * 2654435761ull + (u64)(j1 / R) * 40503ull) % nruns;
-              if (g0 != VM_NONE) out[(r0 * R + (j0 % R)) * wpr + (w0 - j0 * wpr)] = v0;
-              if (g1 != VM_NONE) out[(r1 * R + (j1 % R)) * wpr + (w1 - j1 * wpr)] = v1;
-              continue;
-            }
-#ifdef SS_PART_NT_STORES
-            if (g0 != VM_NONE) __builtin_nontemporal_store(v0, &out[(u64)g0 * wpr + (w0 - j0 * wpr)]);
-            if (g1 != VM_NONE) __builtin_nontemporal_store(v1, &out[(u64)g1 * wpr + (w1 - j1 * wpr)]);
-#else
             if (g0 != VM_NONE) out[(u64)g0 * wpr + (w0 - j0 * wpr)] = v0;
             if (g1 != VM_NONE) out[(u64)g1 * wpr + (w1 - j1 * wpr)] = v1;
-#endif
           }
           WG_BARRIER();
         } break;
@@ -694,28 +638,6 @@
         STOREC_OP(STOREC_8, u8)
         STOREC_OP(STOREC_32, u32)
         STOREC_OP(STOREC_64, u64)
-        case VM_BARRIER: { CASE_FENCE; WG_BARRIER(); } break;
-        STOREG_OP(STOREG_32, u32)
-        STOREG_OP(STOREG_64, u64)
-        case VM_STOREG_8: { CASE_FENCE;      // four output rows per lane: one dword store where all four exist
-          u8* out = reinterpret_cast<u8*>(P.outputs[I.dst].dst);
-          const u32* sc = reinterpret_cast<const u32*>(smem + P.scratch_lds_off);
-          const u32 base = sc[40], end = base + sc[41];
-          const u32* inv = reinterpret_cast<const u32*>(smem + I.b);
-          for (u32 g = (base & ~255u) + 4u * (u32)tp; g < end; g += 4u * VM_COMPUTE_THREADS) {
-            u32 word = 0;
-            _Pragma("unroll") for (u32 j = 0; j < 4; ++j) {
-              const u32 gj = g + j;
-              if (gj >= base && gj < end) word |= (u32)*reinterpret_cast<const u8*>(smem + I.a + (inv[gj - base] & I.a_mask)) << (8u * j);
-            }
-            if (g >= base && g + 4u <= end && ((reinterpret_cast<uintptr_t>(out) & 3u) == 0)) {
-              *reinterpret_cast<u32*>(out + g) = word;
-            } else {
-              _Pragma("unroll") for (u32 j = 0; j < 4; ++j)
-                if (g + j >= base && g + j < end) out[g + j] = (u8)(word >> (8u * j));
-            }
-          }
-        } break;
         case VM_STORE_ROWID: { CASE_FENCE;
           i64* out = reinterpret_cast<i64*>(P.outputs[I.dst].dst);
           _Pragma("unroll") FOR_PAIRS {

@@ -131,7 +131,7 @@ def test_compute_materialize(gpu_ctx, n, nullable):
     run_both(compute_exprs(make_view(n, nullable=nullable)), gpu_ctx)
 
 
-@pytest.mark.parametrize("n", ROWS)
+@pytest.mark.parametrize("n", ROWS + [1000003])
 @pytest.mark.parametrize("k", [-1, 499, 989, 1000])   # all / half / 1% / none pass
 def test_filter_materialize(gpu_ctx, n, k):
     op = ss.Filter(ss.Greater(NA("a"), ss.ConstInt64(k)), ss.ProjectAllAttributes(), ss.ScanView(make_view(n)))
@@ -146,42 +146,25 @@ def test_filter_nullable_predicate_and_project(gpu_ctx, n):
     run_both(op, gpu_ctx)
 
 
-# The one-pass form of the materialising Filter (ctx option filter_single_pass: SEL_RANK_LB's decoupled look-back +
-# LDS-gathered coalesced stores) must give the same rows in the same order as the default count-pass form.
-@pytest.fixture(scope="module")
-def single_pass_ctx():
-    c = ss.Context(0)
-    c.set_option("filter_single_pass", 1)
-    return c
-
-
-@pytest.mark.parametrize("n", ROWS + [1000003])
-@pytest.mark.parametrize("k", [-1, 499, 989, 1000])
-def test_filter_materialize_single_pass(single_pass_ctx, n, k):
-    op = ss.Filter(ss.Greater(NA("a"), ss.ConstInt64(k)), ss.ProjectAllAttributes(), ss.ScanView(make_view(n)))
-    plan = ss.Plan(op, single_pass_ctx)
-    assert "SEL_RANK_LB" in plan.describe() and "SEL_COUNT" not in plan.describe()
-    run_both(op, single_pass_ctx)
-
-
 @pytest.mark.parametrize("n", [0, 65, 1025, 100003])
-def test_filter_single_pass_nullable_and_computed_columns(single_pass_ctx, n):
+def test_filter_nullable_and_computed_columns(gpu_ctx, n):
     view = make_view(n, nullable=True)
     pred = ss.And(ss.Greater(NA("a"), ss.ConstInt64(300)), NA("t"))
-    run_both(ss.Filter(pred, ss.ProjectNamedAttributes(["d", "k1", "a", "d0", "t"]), ss.ScanView(view)), single_pass_ctx)
-    # computed columns: more than one batch of gathers (BARRIER between batches)
+    run_both(ss.Filter(pred, ss.ProjectNamedAttributes(["d", "k1", "a", "d0", "t"]), ss.ScanView(view)), gpu_ctx)
+    # 24 computed columns besides nullable and constant ones
     e = ss.CompoundExpression()
     for i in range(24):
         e.AddAs("x%d" % i, ss.Plus(NA("b"), ss.ConstInt64(i)))
     e.AddAs("h", ss.DivideNulling(NA("d0"), NA("d1"))).Add(NA("k1")).AddAs("five", ss.ConstInt32(5)).Add(NA("c"))
-    run_both(ss.Filter(ss.Less(NA("c"), ss.ConstInt64(40000)), ss.ProjectAllAttributes(), ss.Compute(e, ss.ScanView(view))), single_pass_ctx)
+    run_both(ss.Filter(ss.Less(NA("c"), ss.ConstInt64(40000)), ss.ProjectAllAttributes(), ss.Compute(e, ss.ScanView(view))), gpu_ctx)
 
 
-def test_filter_single_pass_reuses_the_plan(single_pass_ctx):
-    # the look-back words carry a run stamp: a second run over other data must not see the first run's counts
+def test_filter_reuses_the_plan(gpu_ctx):
+    # a second run over other data must not see the first run's tile counts
     views = [make_view(100003, seed=s) for s in (1, 2, 3)]
     op = ss.Filter(ss.Greater(NA("a"), ss.ConstInt64(499)), ss.ProjectAllAttributes(), ss.ScanView(views[0]))
-    plan = ss.Plan(op, single_pass_ctx)
+    plan = ss.Plan(op, gpu_ctx)
+    assert "SEL_COUNT" in plan.describe()
     for v in views:
         plan.run(v)
         got = plan.fetch()
