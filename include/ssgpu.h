@@ -56,7 +56,9 @@
  *     the code in i64).  Code order == the reference's StringPiece order (memcmp, then
  *     length), so comparisons, IN / CASE, MIN / MAX / FIRST / LAST, group keys and sort order
  *     on the codes are bit-exact restatements of the same operations on the strings
- *     (types_infrastructure.h:238-246); the bytes themselves never reach the device.
+ *     (types_infrastructure.h:238-246); the bytes reach the device only when a block encodes
+ *     its own STRING columns there (ssgpu_block_create_from_file / _from_host: the block's dictionary,
+ *     ssgpu_block_dict, which a plan extends with ssgpu_dict_extend and recodes with ssgpu_codes_recode).
  *     Arithmetic, casts and SUM on STRING are bind errors exactly as in the reference.  The
  *     dictionary is ssgpu_dict_* below (the host mirrors build it through the ABI);
  *   - floating aggregates, where results are not bit-defined by the reference's definition:
@@ -386,6 +388,15 @@ int32_t ssgpu_dict_size(const ssgpu_dict* d);
 int ssgpu_dict_encode(const ssgpu_dict* d, const char* const* strings, const int32_t* lengths, const uint8_t* is_null,
                       int64_t n, int32_t* codes);
 int ssgpu_dict_decode(const ssgpu_dict* d, int32_t code, const char** bytes, int32_t* length);
+/* base U strings as a new dictionary; remap[c] (base size entries) = the new code of base code c.  Extending by nothing, or
+ * by values base already holds, gives base's codes unchanged (remap[c] == c). */
+int ssgpu_dict_extend(const ssgpu_dict* base, const char* const* strings, const int32_t* lengths, int64_t n,
+                      ssgpu_dict** out, int32_t* remap);
+/* Device codes through a remap table (host memory, n_remap entries, e.g. ssgpu_dict_extend's): dst[r] = remap[src[r]], 0 for
+ * a NULL row (is_null may be NULL).  src / dst are device pointers of `rows` INT32 cells; runs on the context's stream and
+ * returns once the result is written. */
+int ssgpu_codes_recode(ssgpu_ctx* ctx, const int32_t* src, const uint8_t* is_null, int64_t rows, const int32_t* remap,
+                       int32_t n_remap, int32_t* dst);
 
 /* CONCAT aggregates (column_aggregator.cc:496-505) produce strings that are in no dictionary yet.  The device orders the
  * values (materialise, stable sort by the group keys) and counts them; the strings are printed on the host -- PrintTyped
@@ -434,6 +445,25 @@ int ssgpu_block_column(const ssgpu_block* b, int32_t col, ssgpu_column* out);
 int ssgpu_block_create_from_file(ssgpu_ctx* ctx, const ssgpu_attr* schema, int32_t n_attrs,
                                  const char* path, ssgpu_block** out);
 int ssgpu_block_write_file(ssgpu_block* b, const char* path);
+/* STRING columns of a device block.  A STRING column is stored in the file as  [is_null bytes, if NULLABLE]  [row_count uint64
+ * lengths, 0 for NULL and empty]  [the bytes of the values in one run]  (file_io.cc:122-147,442-474).  ssgpu_block_create_from_file
+ * takes such columns (BINARY stays NOT_IMPLEMENTED): the lengths and bytes travel through the same pinned slabs into HBM, and the
+ * device builds ONE order-preserving dictionary over every STRING column of the block (hash, deduplicate by the full bytes,
+ * sort in StringPiece order: string_dict_kernels.hip), writes the columns' INT32 codes (0 for a NULL row) and copies the distinct
+ * values back once.  The codes depend only on the set of values in the file.  ssgpu_block_create_from_host does the same from
+ * host memory: a STRING column is Arrow-style (offsets[rows + 1] into `data`, `is_null`), other columns are `data` / `is_null`.
+ * ssgpu_block_dict is the dictionary the block's STRING columns are codes of (owned by the block; NULL for a block made any other
+ * way); a plan that scans the block uses it, or an ssgpu_dict_extend of it with ssgpu_codes_recode of the columns.
+ * ssgpu_block_write_file of a block with a dictionary writes its STRING columns in the variable-length layout, so file ->
+ * block -> file gives the same bytes. */
+typedef struct {
+  const void* data;          /* fixed-width: rows cells; STRING: the bytes offsets index */
+  const uint8_t* is_null;    /* NULL = no NULLs */
+  const int64_t* offsets;    /* STRING only: rows + 1 non-decreasing byte offsets into data */
+} ssgpu_host_column;
+int ssgpu_block_create_from_host(ssgpu_ctx* ctx, const ssgpu_attr* schema, int32_t n_attrs, const ssgpu_host_column* cols,
+                                 int64_t rows, ssgpu_block** out);
+const ssgpu_dict* ssgpu_block_dict(const ssgpu_block* b);
 int ssgpu_result_write_file(ssgpu_result* r, const char* path);
 
 /* ---- plan: bind + lower --------------------------------------------------- */

@@ -1792,8 +1792,9 @@ inline FailureOrVoid WriteResultToFile(Cursor* cursor, const std::string& path) 
 }
 
 // FileInput(schema, file, delete_when_done, allocator) drained into device memory: the columns of the whole file as a
-// DeviceView (scan it with ScanDeviceView).  Owns the device block.  Fixed-width columns only: STRING columns have to meet
-// a plan's dictionary on the host first (read them with the host tools, then ScanView).
+// DeviceView (scan it with ScanDeviceView).  Owns the device block.  Fixed-width columns only: the C ABI encodes STRING columns
+// of a file on the device into the block's own dictionary (ssgpu_block_dict), but ScanDeviceView has no way yet to hand a plan
+// that dictionary -- STRING columns are read with the host tools, then ScanView.
 class DeviceTable {
  public:
   ~DeviceTable() { if (block_) ssgpu_block_destroy(block_); }
@@ -1808,6 +1809,9 @@ class DeviceTable {
 
 inline FailureOrOwned<DeviceTable> FileInput(const TupleSchema& schema, const std::string& path, bool delete_when_done = false) {
   ssgpu_ctx* ctx = internal::Context::Get().ctx;
+  for (int i = 0; i < schema.attribute_count(); ++i)
+    if (schema.attribute(i).type() == STRING || schema.attribute(i).type() == BINARY)
+      return FailureOrOwned<DeviceTable>(new Exception(ERROR_NOT_IMPLEMENTED, "FileInput: variable-length columns are read on the host (ScanView)"));
   std::vector<ssgpu_attr> attrs(schema.attribute_count());
   for (int i = 0; i < schema.attribute_count(); ++i) {
     attrs[i].name = schema.attribute(i).name().c_str();

@@ -100,6 +100,10 @@ class Column(C.Structure):
     _fields_ = [("data", C.c_void_p), ("is_null", C.c_void_p)]
 
 
+class HostColumn(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("is_null", C.c_void_p), ("offsets", C.c_void_p)]
+
+
 class PartialSegment(C.Structure):
     _fields_ = [("device_ptr", C.c_void_p), ("count", C.c_int64), ("dtype", C.c_int32), ("reduce", C.c_int32)]
 
@@ -135,6 +139,8 @@ SYMBOLS = [
     ("ssgpu_dict_size", C.c_int32, [P]),
     ("ssgpu_dict_encode", C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), P, C.c_int64, C.POINTER(C.c_int32)]),
     ("ssgpu_dict_decode", C.c_int, [P, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]),
+    ("ssgpu_dict_extend", C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int64, C.POINTER(P), C.POINTER(C.c_int32)]),
+    ("ssgpu_codes_recode", C.c_int, [P, P, P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, P]),
     ("ssgpu_plan_set_memory_limit", C.c_int, [P, C.c_int64]),
     ("ssgpu_plan_set_dict", C.c_int, [P, P]),
     ("ssgpu_result_column_dict", P, [P, C.c_int32]),
@@ -168,6 +174,8 @@ SYMBOLS = [
     ("ssgpu_block_column", C.c_int, [P, C.c_int32, C.POINTER(Column)]),
     ("ssgpu_block_create_from_file", C.c_int, [P, C.POINTER(Attr), C.c_int32, C.c_char_p, C.POINTER(P)]),
     ("ssgpu_block_write_file", C.c_int, [P, C.c_char_p]),
+    ("ssgpu_block_create_from_host", C.c_int, [P, C.POINTER(Attr), C.c_int32, C.POINTER(HostColumn), C.c_int64, C.POINTER(P)]),
+    ("ssgpu_block_dict", P, [P]),
     ("ssgpu_result_write_file", C.c_int, [P, C.c_char_p]),
     ("ssgpu_plan_create", C.c_int, [P, C.POINTER(PlanDesc), C.POINTER(P)]),
     ("ssgpu_plan_destroy", None, [P]),

@@ -66,6 +66,28 @@ class StringDictionary(object):
         self.handle = h
         del self._arr, self._len          # the library copied the bytes
 
+    @classmethod
+    def borrowed(cls, handle, owner):
+        """A view of a dictionary the library owns elsewhere (a device block's, ssgpu_block_dict), kept alive by `owner`."""
+        d = cls.__new__(cls)
+        d.lib = L.load()
+        d.handle = C.c_void_p(handle)
+        d._owner = owner
+        return d
+
+    def extend(self, strings):
+        """self U strings as a new dictionary (ssgpu_dict_extend) -> (dictionary, remap): remap[c] is the new code of code c."""
+        vals = [_as_bytes(v) for v in strings]
+        arr, lens = self._pack(vals)
+        remap = np.zeros(max(len(self), 1), np.int32)
+        h = C.c_void_p()
+        rc = self.lib.ssgpu_dict_extend(self.handle, arr, lens, len(vals), C.byref(h), remap.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != L.OK:
+            raise SupersonicException(rc, "cannot extend the STRING dictionary")
+        d = StringDictionary.__new__(StringDictionary)
+        d.lib, d.handle = self.lib, h
+        return d, remap[:len(self)]
+
     @staticmethod
     def _pack(vals):
         arr = (C.c_char_p * max(len(vals), 1))()
@@ -121,7 +143,7 @@ class StringDictionary(object):
 
     def __del__(self):
         try:
-            if getattr(self, "handle", None):
+            if getattr(self, "handle", None) and not hasattr(self, "_owner"):
                 self.lib.ssgpu_dict_destroy(self.handle)
                 self.handle = None
         except Exception:
@@ -376,6 +398,13 @@ class BlockView(DeviceView):
             ptrs.append((col.data or 0, col.is_null or 0))
         DeviceView.__init__(self, schema, ptrs, lib.ssgpu_block_row_count(block))
 
+    @property
+    def dictionary(self):
+        """The dictionary this block's STRING columns are codes of (ssgpu_block_dict: a block built by FileInput(...,
+        device_strings=True) or BlockFromColumns), or None.  Owned by the block."""
+        h = self._ctx.lib.ssgpu_block_dict(self._block)
+        return StringDictionary.borrowed(h, self) if h else None
+
     def write_file(self, path):
         self._ctx.check(self._ctx.lib.ssgpu_block_write_file(self._block, path.encode()))
 
@@ -479,23 +508,58 @@ def read_view_file(schema, path):
     return View(schema, cols)
 
 
-def FileInput(schema, path, context=None):
+def _attrs_of(schema):
+    return _array(L.Attr, [L.Attr(schema.attribute(i).name().encode(), schema.attribute(i).type(), schema.attribute(i).nullability())
+                           for i in range(schema.attribute_count())])
+
+
+def FileInput(schema, path, context=None, device_strings=False):
     """FileInput(schema, file) drained straight into a device Block: chunks go through pinned
     staging buffers on the copy stream while the next chunk is read (ssgpu_block_create_from_file).
-    Returns a device-resident view usable with ScanView.  A schema with STRING columns is read on the host instead
-    (the values have to meet the plan's dictionary before they can be codes in HBM): the returned host View goes
-    through ScanView's ordinary upload."""
+    Returns a device-resident view usable with ScanView.  A schema with STRING columns is read on the host by default
+    (the returned host View goes through ScanView's ordinary upload); with device_strings=True its STRING columns go to
+    the device as lengths and bytes and are encoded there into the block's own dictionary (BlockView.dictionary).
+    BINARY columns are always read on the host."""
     ctx = context or Context.default()
-    if any(schema.attribute(i).type() in (STRING, BINARY) for i in range(schema.attribute_count())):
+    types = [schema.attribute(i).type() for i in range(schema.attribute_count())]
+    if BINARY in types or (STRING in types and not device_strings):
         return read_view_file(schema, path)
-    attrs = (L.Attr * schema.attribute_count())()
-    keep = []
-    for i in range(schema.attribute_count()):
-        a = schema.attribute(i)
-        name = a.name().encode(); keep.append(name)
-        attrs[i] = L.Attr(name, a.type(), 1 if a.is_nullable() else 0)
+    attrs = _attrs_of(schema)
     block = C.c_void_p()
     ctx.check(ctx.lib.ssgpu_block_create_from_file(ctx.handle, attrs, schema.attribute_count(), path.encode(), C.byref(block)))
+    return BlockView(schema, ctx, block)
+
+
+def BlockFromColumns(schema, columns, context=None):
+    """A device Block from host columns (ssgpu_block_create_from_host): a STRING column is Arrow-style, an (offsets int64[rows + 1],
+    bytes uint8, is_null or None) tuple, and is encoded on the device like FileInput(..., device_strings=True); any other column is
+    its data array or a (data, is_null) pair / Column.  Returns the BlockView (BlockView.dictionary: its dictionary)."""
+    ctx = context or Context.default()
+    n = schema.attribute_count()
+    cols = (L.HostColumn * max(n, 1))()
+    keep, rows = [], None
+    for i in range(n):
+        c = columns[i]
+        if schema.attribute(i).type() == STRING:
+            offsets, data, nulls = (tuple(c) + (None,))[:3]
+            offsets = np.ascontiguousarray(offsets, np.int64)
+            data = np.ascontiguousarray(data, np.uint8)
+            r = len(offsets) - 1
+            cols[i].offsets = offsets.ctypes.data
+            keep.append(offsets)
+        else:
+            data, nulls = (c.data, c.is_null) if isinstance(c, Column) else (c if isinstance(c, tuple) else (c, None))
+            data = np.ascontiguousarray(data, _NP[schema.attribute(i).type()])
+            r = len(data)
+        if rows is not None and r != rows:
+            raise SupersonicException(L.ERROR_INVALID_ARGUMENT_VALUE, "columns of different lengths")
+        rows = r
+        nulls = None if nulls is None else np.ascontiguousarray(nulls, np.bool_)
+        keep += [data, nulls]
+        cols[i].data = data.ctypes.data if data.size else None
+        cols[i].is_null = None if nulls is None else nulls.ctypes.data
+    block = C.c_void_p()
+    ctx.check(ctx.lib.ssgpu_block_create_from_host(ctx.handle, _attrs_of(schema), n, cols, rows or 0, C.byref(block)))
     return BlockView(schema, ctx, block)
 
 
@@ -1030,6 +1094,22 @@ def collect_strings(operation):
     return found
 
 
+def _dict_blocks(operation):
+    """The device blocks with a dictionary of their own (BlockView.dictionary) a plan scans: the ScanView input first."""
+    found = []
+
+    def walk(o):
+        if o is None:
+            return
+        v = getattr(o, "view", None)
+        if isinstance(v, BlockView) and all(v is not f for f in found) and v.dictionary is not None:
+            found.append(v)
+        walk(getattr(o, "child", None))
+        walk(getattr(o, "rhs_child", None))
+    walk(operation)
+    return found
+
+
 def _find_allocator(operation):
     """The allocator set on the nearest operation from the root (SetBufferAllocator cascades downwards)."""
     o = operation
@@ -1111,7 +1191,23 @@ class Plan(object):
         self.ctx = context
         self.lib = context.lib
         b = _Builder()
-        b.strings = self.strings = StringDictionary(list(collect_strings(operation)) + [_as_bytes(v) for v in (extra_strings or [])])
+        strings = list(collect_strings(operation)) + [_as_bytes(v) for v in (extra_strings or [])]
+        # device blocks that built their own dictionary: the plan's is the first one's, extended by everything else the plan meets
+        # (the others' values, constants, host strings); a block whose codes the extension moves is recoded once (_plan_codes)
+        self._recoded, self._base_remap = {}, None
+        blocks = _dict_blocks(operation)
+        if blocks:
+            for other in blocks[1:]:
+                strings += other.dictionary.values
+            base = blocks[0].dictionary
+            self.strings = base
+            if strings:
+                ext, remap = base.extend(strings)
+                if not np.array_equal(remap, np.arange(len(remap))) or len(ext) != len(base):
+                    self.strings, self._base_remap = ext, (blocks[0], remap)
+        else:
+            self.strings = StringDictionary(strings)
+        b.strings = self.strings
         operation._emit(b)
         if b.scan is None:
             raise SupersonicException(L.ERROR_INVALID_ARGUMENT_VALUE, "plan has no ScanView")
@@ -1209,7 +1305,40 @@ class Plan(object):
         return C.string_at(ptr, n.value * nb.value), n.value, nb.value
 
     # -- input staging ------------------------------------------------------------
+    def _plan_codes(self, view):
+        """`view` with STRING columns in codes of this plan's dictionary: a block with a dictionary of its own is recoded on the
+        device (once per block; ssgpu_codes_recode), or refused with ERROR_INVALID_ARGUMENT_VALUE when it holds a value the plan's
+        dictionary lacks -- a plan never runs on codes of another dictionary."""
+        d = view.dictionary
+        if d is None or d.handle.value == self.strings.handle.value:
+            return view
+        hit = self._recoded.get(id(view))
+        if hit is not None and hit[0] is view:
+            return hit[1]
+        if self._base_remap is not None and self._base_remap[0] is view:
+            remap = self._base_remap[1]
+        else:
+            remap = self.strings.encode(d.values, None)      # raises for a value outside the plan's dictionary
+        out = view
+        if not np.array_equal(remap, np.arange(len(remap))):
+            schema, rows = view.schema(), view.row_count()
+            idx = [i for i in range(schema.attribute_count()) if schema.attribute(i).type() == STRING]
+            blk = DeviceBlock(TupleSchema([Attribute("c%d" % i, INT32) for i in idx]), max(rows, 1), self.ctx)
+            remap = np.ascontiguousarray(remap, np.int32)
+            ptrs = list(view._ptrs)
+            for j, i in enumerate(idx):
+                dp, npn = view._ptrs[i]
+                self.ctx.check(self.lib.ssgpu_codes_recode(self.ctx.handle, dp, npn or None, rows, remap.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           len(remap), blk.column_ptr(j)))
+                ptrs[i] = (blk.column_ptr(j), npn)
+            out = DeviceView(schema, ptrs, rows)
+            out._owner = (view, blk)
+        self._recoded[id(view)] = (view, out)
+        return out
+
     def _columns_for(self, view, slot="_block"):
+        if isinstance(view, BlockView) and hasattr(self, "_recoded"):
+            view = self._plan_codes(view)
         if isinstance(view, DeviceView):
             cols = (L.Column * max(len(view._ptrs), 1))()
             for i, (dp, npn) in enumerate(view._ptrs):

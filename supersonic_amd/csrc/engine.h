@@ -17,6 +17,10 @@
 #include "vm.h"
 #include "launch.h"
 
+// seams.cpp: a dictionary over values already sorted and unique (`offsets[n + 1]` into `heap`), taken without sorting again --
+// how the distinct strings a device block's STRING columns were encoded with come back to the host
+extern "C" int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offsets, int64_t n, ssgpu_dict** out);
+
 namespace ssgpu {
 
 struct Status {

@@ -314,6 +314,25 @@ hipError_t ssgpu_launch_sort_extract_idx(uint32_t* idx, const uint64_t* kc, uint
 // View-file loader: one piece = one column (or NULL-mask) segment of one file chunk inside a staged slab
 struct UnpackPiece { unsigned long long src_off; void* dst; unsigned long long bytes; };
 hipError_t ssgpu_launch_unpack(const char* slab, const UnpackPiece* pieces, unsigned int n_pieces, hipStream_t s);
+// STRING dictionary over a string domain (string_dict_kernels.hip): lengths -> offsets (exclusive scan, data[n] = total; `partials`
+// holds ssgpu_str_scan_partials(n) words), hash, insert into an open-addressing table of `cap` (a power of two) zeroed words,
+// compact the occupied slots (count zeroed), sort the distinct strings, rank, codes, gather the distinct bytes in code order
+uint64_t ssgpu_str_scan_partials(uint64_t n);
+hipError_t ssgpu_launch_str_scan(uint64_t* data, uint64_t n, uint64_t* partials, hipStream_t s);
+hipError_t ssgpu_launch_str_hash(const uint8_t* bytes, const uint64_t* offs, const uint8_t* nulls, uint64_t n, uint64_t* hashes, hipStream_t s);
+hipError_t ssgpu_launch_str_insert(const uint8_t* bytes, const uint64_t* offs, const uint8_t* nulls, const uint64_t* hashes, uint64_t n,
+                                   uint64_t* table, uint64_t cap, uint32_t* row_slot, uint32_t* error, hipStream_t s);
+hipError_t ssgpu_launch_str_compact(const uint64_t* table, uint64_t cap, const uint8_t* bytes, const uint64_t* offs, uint32_t* count,
+                                    uint32_t* d_slot, uint64_t* d_off, uint64_t* d_len, uint64_t* d_key, uint32_t* d_idx, hipStream_t s);
+hipError_t ssgpu_launch_str_sort(uint64_t* d_key, uint32_t* d_idx, uint64_t d, uint64_t p, const uint8_t* bytes, const uint64_t* d_off,
+                                 const uint64_t* d_len, hipStream_t s);
+hipError_t ssgpu_launch_str_rank(const uint32_t* d_idx, const uint32_t* d_slot, const uint64_t* d_len, uint64_t d, int32_t* slot_rank,
+                                 uint64_t* out_len, hipStream_t s);
+hipError_t ssgpu_launch_str_codes(const uint32_t* row_slot, const uint8_t* nulls, const int32_t* slot_rank, uint64_t n, int32_t* codes, hipStream_t s);
+hipError_t ssgpu_launch_str_gather(const uint8_t* bytes, const uint64_t* d_off, const uint32_t* d_idx, const uint64_t* out_off, uint64_t d,
+                                   uint8_t* out, hipStream_t s);
+hipError_t ssgpu_launch_str_recode(const int32_t* src, const uint8_t* nulls, const int32_t* remap, int32_t n_remap, uint64_t n, int32_t* dst,
+                                   hipStream_t s);
 hipError_t ssgpu_launch_sort_unkey(void* out, const uint64_t* keys, uint32_t width, int kind, int descending, uint64_t n, hipStream_t s);
 hipError_t ssgpu_launch_sort_gather(void* out, uint8_t* out_nulls, const void* col, const uint8_t* nulls, uint32_t width,
                                     const uint32_t* idx, uint64_t n, hipStream_t s);

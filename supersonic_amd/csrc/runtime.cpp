@@ -440,6 +440,7 @@ struct ssgpu_block {
   // `nulls` are views into it.
   DevBuf arena;
   std::vector<DevBuf> data, nulls;
+  ssgpu_dict* dict = nullptr;   // the dictionary the STRING columns are codes of, when the block built it (ssgpu_block_dict)
 };
 static const size_t kBlockColumnSkew = 512, kBlockArenaMin = 32u << 20;
 
@@ -604,7 +605,7 @@ int ssgpu_block_create(ssgpu_ctx* c, const ssgpu_attr* schema, int32_t n, int64_
   *out = b;
   return SSGPU_OK;
 }
-void ssgpu_block_destroy(ssgpu_block* b) { if (!b) return; ssgpu_ctx* c = b->ctx; delete b; g_live_blocks.fetch_sub(1); if (c) ctx_release(c); }
+void ssgpu_block_destroy(ssgpu_block* b) { if (!b) return; ssgpu_ctx* c = b->ctx; ssgpu_dict_destroy(b->dict); delete b; g_live_blocks.fetch_sub(1); if (c) ctx_release(c); }
 
 // ---- View file format: cursor/infrastructure/file_io.cc ---------------------------------------
 static const int64_t kFileChunkRows = 8192;   // kMaxChunkRowCount, file_io.cc:70
@@ -632,54 +633,143 @@ static bool read_slab(FILE* f, char* dst, size_t bytes) {
   return ok && fseek(f, pos + (long)bytes, SEEK_SET) == 0;
 }
 
+// ---- STRING columns: one dictionary over every STRING column of a block (string_dict_kernels.hip) ------------------------
+// The domain is the block's STRING columns end to end (column k's row r is domain row k x rows + r).  `lens` holds domain + 1
+// words: the byte lengths, scanned here into offsets into `heap`; `dnull` one NULL byte per domain row.  Runs on the copy
+// stream, writes the codes into the block's STRING columns and gives the block its dictionary.
+static const int64_t kMaxStringDomain = int64_t(1) << 30;   // the table's slot numbers stay 32-bit
+static int encode_string_domain(ssgpu_ctx* c, ssgpu_block* b, const std::vector<int>& scols, DevBuf& heap, DevBuf& lens, DevBuf& dnull) {
+  hipStream_t s = c->copy_stream;
+  const uint64_t rows = (uint64_t)b->rows, n = rows * scols.size();
+  std::vector<uint64_t> off_h(1, 0);
+  std::vector<char> heap_h;
+  uint32_t D = 0;
+  if (n) {
+    uint64_t cap = 64, np2 = 1;
+    while (cap < 2 * n) cap <<= 1;
+    while (np2 < n) np2 <<= 1;
+    DevBuf partials, hashes, table, row_slot, flags, d_slot, d_off, d_len, d_key, d_idx, slot_rank, out_off, out_heap;
+    const bool alloc_ok =
+        partials.ensure(ssgpu_str_scan_partials(n) * 8) == hipSuccess && hashes.ensure(n * 8) == hipSuccess && table.ensure(cap * 8) == hipSuccess &&
+        row_slot.ensure(n * 4) == hipSuccess && flags.ensure(8) == hipSuccess && d_slot.ensure(n * 4) == hipSuccess && d_off.ensure(n * 8) == hipSuccess &&
+        d_len.ensure(n * 8) == hipSuccess && d_key.ensure(np2 * 8) == hipSuccess && d_idx.ensure(np2 * 4) == hipSuccess &&
+        slot_rank.ensure(cap * 4) == hipSuccess && out_off.ensure((n + 1) * 8) == hipSuccess;
+    if (!alloc_ok) { c->err = "Memory exceeded: the STRING dictionary's device tables"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
+    const uint8_t* bytes = heap.as<uint8_t>();
+    const uint64_t* offs = lens.as<uint64_t>();
+    HIP_TRY(c, ssgpu_launch_str_scan(lens.as<uint64_t>(), n, partials.as<uint64_t>(), s));
+    HIP_TRY(c, ssgpu_launch_str_hash(bytes, offs, dnull.as<uint8_t>(), n, hashes.as<uint64_t>(), s));
+    HIP_TRY(c, hipMemsetAsync(table.p, 0, cap * 8, s));
+    HIP_TRY(c, hipMemsetAsync(flags.p, 0, 8, s));
+    HIP_TRY(c, ssgpu_launch_str_insert(bytes, offs, dnull.as<uint8_t>(), hashes.as<uint64_t>(), n, table.as<uint64_t>(), cap, row_slot.as<uint32_t>(),
+                                       flags.as<uint32_t>() + 1, s));
+    HIP_TRY(c, ssgpu_launch_str_compact(table.as<uint64_t>(), cap, bytes, offs, flags.as<uint32_t>(), d_slot.as<uint32_t>(), d_off.as<uint64_t>(),
+                                        d_len.as<uint64_t>(), d_key.as<uint64_t>(), d_idx.as<uint32_t>(), s));
+    uint32_t fl[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(fl, flags.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (fl[1]) { c->err = "STRING dictionary: hash table overflow"; return SSGPU_ERROR_UNKNOWN; }
+    D = fl[0];
+    uint64_t p2 = 1;
+    while (p2 < D) p2 <<= 1;
+    HIP_TRY(c, ssgpu_launch_str_sort(d_key.as<uint64_t>(), d_idx.as<uint32_t>(), D, D ? p2 : 0, bytes, d_off.as<uint64_t>(), d_len.as<uint64_t>(), s));
+    HIP_TRY(c, ssgpu_launch_str_rank(d_idx.as<uint32_t>(), d_slot.as<uint32_t>(), d_len.as<uint64_t>(), D, slot_rank.as<int32_t>(), out_off.as<uint64_t>(), s));
+    HIP_TRY(c, ssgpu_launch_str_scan(out_off.as<uint64_t>(), D, partials.as<uint64_t>(), s));
+    for (size_t k = 0; k < scols.size(); ++k)
+      HIP_TRY(c, ssgpu_launch_str_codes(row_slot.as<uint32_t>() + k * rows, dnull.as<uint8_t>() + k * rows, slot_rank.as<int32_t>(), rows,
+                                        b->data[scols[k]].as<int32_t>(), s));
+    off_h.resize((size_t)D + 1);
+    HIP_TRY(c, hipMemcpyAsync(off_h.data(), out_off.p, ((size_t)D + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (out_heap.ensure(std::max<uint64_t>(off_h[D], 1)) != hipSuccess) { c->err = "Memory exceeded: the STRING dictionary's values"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
+    HIP_TRY(c, ssgpu_launch_str_gather(bytes, d_off.as<uint64_t>(), d_idx.as<uint32_t>(), out_off.as<uint64_t>(), D, out_heap.as<uint8_t>(), s));
+    heap_h.resize((size_t)off_h[D]);
+    if (off_h[D]) HIP_TRY(c, hipMemcpyAsync(heap_h.data(), out_heap.p, (size_t)off_h[D], hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+  }
+  ssgpu_dict* d = nullptr;
+  const int rc = ssgpu_dict_create_sorted(heap_h.data(), off_h.data(), (int64_t)D, &d);
+  if (rc != SSGPU_OK) { c->err = "STRING dictionary: too many distinct values"; return rc; }
+  ssgpu_dict_destroy(b->dict);
+  b->dict = d;
+  return SSGPU_OK;
+}
+
 int ssgpu_block_create_from_file(ssgpu_ctx* c, const ssgpu_attr* schema, int32_t n, const char* path, ssgpu_block** out) {
   if (!c || c->device < 0) return SSGPU_ERROR_NO_DEVICE;
   FILE* f = path ? fopen(path, "rb") : nullptr;
   if (!f) { c->err = std::string("cannot open ") + (path ? path : "(null)"); return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
-  std::vector<int> width(n); std::vector<bool> nullable(n);
-  int64_t row_bytes = 0;
+  std::vector<int> width(n); std::vector<bool> nullable(n), is_str(n);
+  std::vector<int> scols;            // STRING columns, in schema order: the dictionary's domain
   for (int i = 0; i < n; ++i) {
-    width[i] = dtype_width(schema[i].dtype); nullable[i] = schema[i].nullable != 0;
-    if (width[i] == 0 || schema[i].dtype == SSGPU_STRING) { fclose(f); c->err = "variable-length columns of the file format are outside the device hot path"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
-    row_bytes += width[i] + (nullable[i] ? 1 : 0);
+    width[i] = dtype_width(schema[i].dtype); nullable[i] = schema[i].nullable != 0; is_str[i] = schema[i].dtype == SSGPU_STRING;
+    if (width[i] == 0) { fclose(f); c->err = "variable-length columns of the file format are outside the device hot path"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
+    if (is_str[i]) scols.push_back(i);
   }
-  // pass 1: chunk headers only (the payload size follows from the row count and the schema)
-  int64_t total = 0; uint64_t rc = 0;
-  std::vector<uint64_t> chunk_rows;
-  bool header_ok = true; const char* header_why = "";
+  const size_t ns = scols.size();
+  fseek(f, 0, SEEK_END);
+  const int64_t fsize = (int64_t)ftell(f);
+  rewind(f);
+  // pass 1: chunk headers (the payload size follows from the row count and the schema) and, for STRING columns, their lengths
+  int64_t total = 0, pos = 0; uint64_t rc = 0;
+  std::vector<uint64_t> chunk_rows, chunk_bytes, chunk_sbytes;   // chunk_sbytes: ns words per chunk, the bytes of each STRING column's values
+  std::vector<uint64_t> col_bytes(ns, 0), lens;
+  bool header_ok = true, body_ok = true; const char* header_why = "";
   while (fread(&rc, 8, 1, f) == 1) {
     // a chunk never holds more than kMaxChunkRowCount rows (file_io.cc:70): anything else is a corrupt header, and
     // trusting it would seek by a garbage (possibly negative) distance
     if (rc == 0 || rc > (uint64_t)kFileChunkRows) { header_ok = false; header_why = rc == 0 ? " Chunk of size 0." : " Input chunk too large."; break; }   // file_io.cc:398-409
-    if (fseek(f, (long)((int64_t)rc * row_bytes), SEEK_CUR) != 0) break;
-    total += (int64_t)rc; chunk_rows.push_back(rc);
+    const int64_t start_pos = pos;
+    pos += 8;
+    for (int i = 0, k = 0; i < n && body_ok; ++i) {
+      if (nullable[i]) pos += (int64_t)rc;
+      if (!is_str[i]) { pos += (int64_t)rc * width[i]; continue; }
+      // ReadVariableLengthData (file_io.cc:442-474): rc uint64 lengths, then their sum of bytes -- which must lie inside the file
+      lens.resize(rc);
+      body_ok = pos + (int64_t)rc * 8 <= fsize && fseek(f, (long)pos, SEEK_SET) == 0 && fread(lens.data(), 8, rc, f) == rc;
+      pos += (int64_t)rc * 8;
+      uint64_t sum = 0;
+      for (uint64_t j = 0; j < rc && body_ok; ++j) { body_ok = lens[j] <= (uint64_t)(fsize - pos) - sum; sum += lens[j]; }
+      pos += (int64_t)sum;
+      chunk_sbytes.push_back(sum); col_bytes[k++] += sum;
+    }
+    if (!body_ok || pos > fsize || fseek(f, (long)pos, SEEK_SET) != 0) { body_ok = false; break; }
+    total += (int64_t)rc; chunk_rows.push_back(rc); chunk_bytes.push_back((uint64_t)(pos - start_pos));
   }
   if (!header_ok) { fclose(f); c->err = std::string("Reading cursor's data from the input file failed.") + header_why; return SSGPU_ERROR_GENERAL_IO_ERROR; }
-  { const long end = ftell(f); fseek(f, 0, SEEK_END); if (ftell(f) < end) { fclose(f); c->err = "Reading cursor's data from the input file failed."; return SSGPU_ERROR_GENERAL_IO_ERROR; } }
+  if (!body_ok) { fclose(f); c->err = "Reading cursor's data from the input file failed."; return SSGPU_ERROR_GENERAL_IO_ERROR; }
+  if (total * (int64_t)ns > kMaxStringDomain) { fclose(f); c->err = "more than 2^30 STRING cells in one block"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
   rewind(f);
   ssgpu_block* b = nullptr;
   int rcode = ssgpu_block_create(c, schema, n, std::max<int64_t>(total, 1), &b);
   if (rcode != SSGPU_OK) { fclose(f); return rcode; }
+  // the STRING domain: lengths (column after column), one heap of bytes, one NULL byte per cell
+  DevBuf dlens, dheap, dnull;
+  std::vector<uint64_t> col_base(ns, 0), col_fill(ns, 0);
+  uint64_t heap_bytes = 0;
+  for (size_t k = 0; k < ns; ++k) { col_base[k] = heap_bytes; heap_bytes += col_bytes[k]; }
+  bool ok = true;
+  if (ns) ok = dlens.ensure(((size_t)total * ns + 1) * 8) == hipSuccess && dheap.ensure(heap_bytes + 8) == hipSuccess &&
+               dnull.ensure(std::max<size_t>((size_t)total * ns, 1)) == hipSuccess;
+  if (!ok) { fclose(f); ssgpu_block_destroy(b); c->err = "Memory exceeded: the STRING columns' lengths and bytes"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
   // pass 2: two pinned slabs of whole chunks (headers included, >= 32 MiB or one chunk).  A slab crosses PCIe
   // as ONE copy into a device slab and a kernel scatters its column pieces (the format interleaves a few KiB
   // per column per chunk: tens of thousands of small copies per GB otherwise); slab k+1 is read from the file
   // while slab k is copied and unpacked on the copy stream.
   size_t slab_bytes = 32u << 20, max_pieces = 1;
-  for (uint64_t r : chunk_rows) slab_bytes = std::max(slab_bytes, (size_t)8 + (size_t)r * (size_t)row_bytes);
+  for (uint64_t cb : chunk_bytes) slab_bytes = std::max(slab_bytes, (size_t)cb);
   PinnedBuf stage[2], table[2]; DevBuf dslab[2], dtable[2]; hipEvent_t done[2] = {nullptr, nullptr};
-  int64_t off = 0; int k = 0; bool ok = true;
+  int64_t off = 0; int k = 0;
   { size_t run = 0, cnt = 0;   // most chunks that can share a slab
-    for (uint64_t r : chunk_rows) { const size_t b8 = 8 + (size_t)r * (size_t)row_bytes; if (run + b8 > slab_bytes) { max_pieces = std::max(max_pieces, cnt); run = 0; cnt = 0; } run += b8; ++cnt; }
-    max_pieces = std::max(max_pieces, cnt) * (size_t)(2 * n); }
+    for (uint64_t cb : chunk_bytes) { if (run + cb > slab_bytes) { max_pieces = std::max(max_pieces, cnt); run = 0; cnt = 0; } run += cb; ++cnt; }
+    max_pieces = std::max(max_pieces, cnt) * (size_t)(3 * n); }
   for (int i = 0; i < 2 && ok; ++i)
     ok = stage[i].ensure(slab_bytes) == hipSuccess && table[i].ensure(max_pieces * sizeof(UnpackPiece)) == hipSuccess &&
          dslab[i].ensure(slab_bytes) == hipSuccess && dtable[i].ensure(max_pieces * sizeof(UnpackPiece)) == hipSuccess &&
          hipEventCreateWithFlags(&done[i], hipEventDisableTiming) == hipSuccess;
   for (size_t ci = 0; ok && ci < chunk_rows.size();) {
     size_t take = 0, bytes = 0;
-    while (ci + take < chunk_rows.size() && bytes + 8 + (size_t)chunk_rows[ci + take] * (size_t)row_bytes <= slab_bytes) {
-      bytes += 8 + (size_t)chunk_rows[ci + take] * (size_t)row_bytes; ++take;
-    }
+    while (ci + take < chunk_rows.size() && bytes + chunk_bytes[ci + take] <= slab_bytes) { bytes += chunk_bytes[ci + take]; ++take; }
     if (hipEventSynchronize(done[k]) != hipSuccess) { ok = false; break; }   // slab k (host and device) free again
     char* base = reinterpret_cast<char*>(stage[k].p);
     if (!read_slab(f, base, bytes)) { ok = false; break; }
@@ -689,10 +779,22 @@ int ssgpu_block_create_from_file(ssgpu_ctx* c, const ssgpu_attr* schema, int32_t
     for (size_t j = 0; j < take && ok; ++j) {
       uint64_t rows_here; memcpy(&rows_here, p, 8); p += 8;
       if (rows_here != chunk_rows[ci + j]) { ok = false; break; }
-      for (int i = 0; i < n; ++i) {
+      for (int i = 0, sk = 0; i < n && ok; ++i) {
         if (nullable[i]) { pieces[np++] = {(unsigned long long)(p - base), (char*)b->nulls[i].p + off, rows_here}; p += rows_here; }
-        pieces[np++] = {(unsigned long long)(p - base), (char*)b->data[i].p + off * width[i], rows_here * (uint64_t)width[i]};
-        p += (size_t)rows_here * width[i];
+        if (!is_str[i]) {
+          pieces[np++] = {(unsigned long long)(p - base), (char*)b->data[i].p + off * width[i], rows_here * (uint64_t)width[i]};
+          p += (size_t)rows_here * width[i];
+          continue;
+        }
+        // (the file is read twice: the lengths must still add up to what pass 1 sized the heap for)
+        const uint64_t sbytes = chunk_sbytes[(ci + j) * ns + sk];
+        uint64_t sum = 0, len;
+        for (uint64_t r = 0; r < rows_here; ++r) { memcpy(&len, p + r * 8, 8); sum += len; }
+        if (sum != sbytes) { ok = false; break; }
+        pieces[np++] = {(unsigned long long)(p - base), (char*)dlens.p + ((uint64_t)sk * total + off) * 8, rows_here * 8};
+        p += (size_t)rows_here * 8;
+        pieces[np++] = {(unsigned long long)(p - base), (char*)dheap.p + col_base[sk] + col_fill[sk], sbytes};
+        p += sbytes; col_fill[sk] += sbytes; ++sk;
       }
       off += (int64_t)rows_here;
     }
@@ -703,19 +805,107 @@ int ssgpu_block_create_from_file(ssgpu_ctx* c, const ssgpu_attr* schema, int32_t
     ci += take; k ^= 1;
   }
   fclose(f);
+  // every STRING cell's NULL byte, in domain order (a NOT_NULLABLE column has none)
+  for (size_t sk = 0; ok && sk < ns; ++sk) {
+    char* dst = (char*)dnull.p + sk * (size_t)total;
+    ok = (nullable[scols[sk]] ? hipMemcpyAsync(dst, b->nulls[scols[sk]].p, (size_t)total, hipMemcpyDeviceToDevice, c->copy_stream)
+                              : hipMemsetAsync(dst, 0, (size_t)total, c->copy_stream)) == hipSuccess;
+  }
   if (ok) ok = hipStreamSynchronize(c->copy_stream) == hipSuccess;
   for (int i = 0; i < 2; ++i) if (done[i]) (void)hipEventDestroy(done[i]);
   if (!ok || off != total) { ssgpu_block_destroy(b); c->err = "Reading cursor's data from the input file failed."; return SSGPU_ERROR_GENERAL_IO_ERROR; }
   b->rows = total;
+  if (ns) {
+    const int erc = encode_string_domain(c, b, scols, dheap, dlens, dnull);
+    if (erc != SSGPU_OK) { ssgpu_block_destroy(b); return erc; }
+  }
   *out = b;
   return SSGPU_OK;
 }
 
+int ssgpu_block_create_from_host(ssgpu_ctx* c, const ssgpu_attr* schema, int32_t n, const ssgpu_host_column* cols, int64_t rows, ssgpu_block** out) {
+  if (!c || c->device < 0) return SSGPU_ERROR_NO_DEVICE;
+  if (!schema || !out || n < 0 || rows < 0 || (n > 0 && !cols)) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  std::vector<int> scols;
+  for (int i = 0; i < n; ++i) {
+    if (dtype_width(schema[i].dtype) == 0) { c->err = "variable-length columns other than STRING are outside the device hot path"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
+    if (schema[i].dtype != SSGPU_STRING) {
+      if (rows && !cols[i].data) { c->err = "column without data"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+      continue;
+    }
+    const int64_t* o = cols[i].offsets;
+    if (!o) { c->err = "a STRING column needs offsets[rows + 1]"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+    if (o[0] < 0) { c->err = "STRING offsets must not be negative"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+    for (int64_t r = 0; r < rows; ++r) if (o[r + 1] < o[r]) { c->err = "STRING offsets must not decrease"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+    if (o[rows] > o[0] && !cols[i].data) { c->err = "column without data"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+    scols.push_back(i);
+  }
+  const size_t ns = scols.size();
+  if (rows * (int64_t)ns > kMaxStringDomain) { c->err = "more than 2^30 STRING cells in one block"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
+  ssgpu_block* b = nullptr;
+  int rcode = ssgpu_block_create(c, schema, n, std::max<int64_t>(rows, 1), &b);
+  if (rcode != SSGPU_OK) return rcode;
+  hipStream_t s = c->copy_stream;
+  uint64_t heap_bytes = 0;
+  for (int i : scols) heap_bytes += (uint64_t)(cols[i].offsets[rows] - cols[i].offsets[0]);
+  DevBuf dlens, dheap, dnull;
+  std::vector<uint64_t> lens(ns ? (size_t)rows * ns + 1 : 0, 0);
+  bool ok = !ns || (dlens.ensure(lens.size() * 8) == hipSuccess && dheap.ensure(heap_bytes + 8) == hipSuccess &&
+                    dnull.ensure(std::max<size_t>((size_t)rows * ns, 1)) == hipSuccess);
+  if (!ok) { ssgpu_block_destroy(b); c->err = "Memory exceeded: the STRING columns' lengths and bytes"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
+  uint64_t heap_off = 0;
+  for (int i = 0, sk = 0; i < n && ok && rows; ++i) {
+    if (schema[i].nullable) ok = (cols[i].is_null ? hipMemcpyAsync(b->nulls[i].p, cols[i].is_null, (size_t)rows, hipMemcpyHostToDevice, s)
+                                                  : hipMemsetAsync(b->nulls[i].p, 0, (size_t)rows, s)) == hipSuccess;
+    if (!ok) break;
+    if (schema[i].dtype != SSGPU_STRING) {
+      ok = hipMemcpyAsync(b->data[i].p, cols[i].data, (size_t)rows * dtype_width(schema[i].dtype), hipMemcpyHostToDevice, s) == hipSuccess;
+      continue;
+    }
+    const int64_t* o = cols[i].offsets;
+    for (int64_t r = 0; r < rows; ++r) lens[(size_t)sk * rows + r] = (uint64_t)(o[r + 1] - o[r]);
+    const uint64_t nb = (uint64_t)(o[rows] - o[0]);
+    char* nd = (char*)dnull.p + (size_t)sk * rows;
+    if (nb) ok = hipMemcpyAsync((char*)dheap.p + heap_off, (const char*)cols[i].data + o[0], nb, hipMemcpyHostToDevice, s) == hipSuccess;
+    // (a NOT_NULLABLE column's is_null, if given, is ignored, as the block keeps no mask for it)
+    if (ok) ok = (schema[i].nullable && cols[i].is_null ? hipMemcpyAsync(nd, cols[i].is_null, (size_t)rows, hipMemcpyHostToDevice, s)
+                                                        : hipMemsetAsync(nd, 0, (size_t)rows, s)) == hipSuccess;
+    heap_off += nb; ++sk;
+  }
+  if (ok && ns && rows) ok = hipMemcpyAsync(dlens.p, lens.data(), lens.size() * 8, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (ok) ok = hipStreamSynchronize(s) == hipSuccess;
+  if (!ok) { ssgpu_block_destroy(b); c->err = "copying the host columns to the device failed"; return SSGPU_ERROR_HIP; }
+  b->rows = rows;
+  if (ns) {
+    const int erc = encode_string_domain(c, b, scols, dheap, dlens, dnull);
+    if (erc != SSGPU_OK) { ssgpu_block_destroy(b); return erc; }
+  }
+  *out = b;
+  return SSGPU_OK;
+}
+
+const ssgpu_dict* ssgpu_block_dict(const ssgpu_block* b) { return b ? b->dict : nullptr; }
+
+int ssgpu_codes_recode(ssgpu_ctx* c, const int32_t* src, const uint8_t* is_null, int64_t rows, const int32_t* remap, int32_t n_remap, int32_t* dst) {
+  if (!c || c->device < 0) return SSGPU_ERROR_NO_DEVICE;
+  if (rows < 0 || n_remap < 0 || (rows > 0 && (!src || !dst)) || (n_remap > 0 && !remap)) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  if (!rows) return SSGPU_OK;
+  DevBuf dremap;
+  HIP_TRY(c, dremap.ensure(std::max<size_t>((size_t)n_remap * 4, 4)));
+  if (c->copy_pending.load(std::memory_order_acquire)) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));   // (block uploads before it)
+  if (n_remap) HIP_TRY(c, hipMemcpyAsync(dremap.p, remap, (size_t)n_remap * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, ssgpu_launch_str_recode(src, is_null, dremap.as<int32_t>(), n_remap, (uint64_t)rows, dst, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the remap table goes when this returns)
+  return SSGPU_OK;
+}
+// `dict` (a block's, ssgpu_block_dict): its STRING columns leave in the variable-length layout instead of as codes
 static int write_view_file(ssgpu_ctx* c, const char* path, int n, int64_t rows, const std::vector<const void*>& dev_data,
-                           const std::vector<const uint8_t*>& dev_nulls, const std::vector<int>& width, const std::vector<bool>& nullable) {
+                           const std::vector<const uint8_t*>& dev_nulls, const std::vector<int>& width, const std::vector<bool>& nullable,
+                           const ssgpu_dict* dict = nullptr, const std::vector<bool>& is_str = std::vector<bool>()) {
   FILE* f = path ? fopen(path, "wb") : nullptr;
   if (!f) { c->err = "Writing view to the output file failed."; return SSGPU_ERROR_GENERAL_IO_ERROR; }
   std::vector<char> host;
+  std::vector<int32_t> codes; std::vector<uint64_t> lens; std::string run;
   bool ok = true;
   for (int64_t off = 0; off < rows && ok; off += kFileChunkRows) {
     const uint64_t rc = (uint64_t)std::min<int64_t>(kFileChunkRows, rows - off);
@@ -725,6 +915,20 @@ static int write_view_file(ssgpu_ctx* c, const char* path, int n, int64_t rows, 
         host.assign((size_t)rc, 0);
         if (dev_nulls[i]) ok = hipMemcpy(host.data(), dev_nulls[i] + off, (size_t)rc, hipMemcpyDeviceToHost) == hipSuccess;
         ok = ok && fwrite(host.data(), 1, (size_t)rc, f) == (size_t)rc;
+      }
+      if (dict && is_str[i]) {
+        // WriteVariableLengthData (file_io.cc:122-147): a uint64 length per row, 0 for NULL and empty, then the bytes in one run
+        codes.resize((size_t)rc);
+        ok = ok && hipMemcpy(codes.data(), reinterpret_cast<const char*>(dev_data[i]) + off * 4, (size_t)rc * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        lens.assign((size_t)rc, 0); run.clear();
+        for (uint64_t r = 0; r < rc && ok; ++r) {
+          if (nullable[i] && host[r]) continue;
+          const char* v; int32_t len;
+          ok = ssgpu_dict_decode(dict, codes[r], &v, &len) == SSGPU_OK;
+          if (ok) { lens[r] = (uint64_t)len; run.append(v, (size_t)len); }
+        }
+        ok = ok && fwrite(lens.data(), 8, (size_t)rc, f) == (size_t)rc && fwrite(run.data(), 1, run.size(), f) == run.size();
+        continue;
       }
       host.resize((size_t)rc * width[i]);
       ok = ok && hipMemcpy(host.data(), reinterpret_cast<const char*>(dev_data[i]) + off * width[i], host.size(), hipMemcpyDeviceToHost) == hipSuccess;
@@ -742,8 +946,9 @@ int ssgpu_block_write_file(ssgpu_block* b, const char* path) {
   HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
   const int n = (int)b->schema.size();
   std::vector<const void*> d(n); std::vector<const uint8_t*> z(n); std::vector<int> w(n); std::vector<bool> nl(n);
-  for (int i = 0; i < n; ++i) { d[i] = b->data[i].p; z[i] = b->schema[i].nullable ? b->nulls[i].as<uint8_t>() : nullptr; w[i] = dtype_width(b->schema[i].dtype); nl[i] = b->schema[i].nullable; }
-  return write_view_file(c, path, n, b->rows, d, z, w, nl);
+  std::vector<bool> st(n);
+  for (int i = 0; i < n; ++i) { d[i] = b->data[i].p; z[i] = b->schema[i].nullable ? b->nulls[i].as<uint8_t>() : nullptr; w[i] = dtype_width(b->schema[i].dtype); nl[i] = b->schema[i].nullable; st[i] = b->schema[i].dtype == SSGPU_STRING; }
+  return write_view_file(c, path, n, b->rows, d, z, w, nl, b->dict, st);
 }
 
 int ssgpu_block_upload(ssgpu_block* b, int32_t col, const void* hd, const uint8_t* hn, int64_t off, int64_t rows) {

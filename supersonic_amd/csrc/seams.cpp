@@ -7,7 +7,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <iterator>
 #include <limits>
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -110,7 +112,14 @@ void ssgpu_allocator_free(ssgpu_allocator* a, void* p) {
 // ---- order-preserving dictionary ---------------------------------------------------------------------------------
 struct ssgpu_dict {
   std::vector<std::string> values;                  // sorted: memcmp, then length == std::string's operator< on bytes
-  std::unordered_map<std::string, int32_t> code;
+  // value -> code, built on first use: a dictionary made on the device for a block is often only decoded, never looked up
+  const std::unordered_map<std::string, int32_t>& codes() const {
+    std::call_once(code_once, [this] { code.reserve(values.size()); for (size_t i = 0; i < values.size(); ++i) code[values[i]] = (int32_t)i; });
+    return code;
+  }
+ private:
+  mutable std::once_flag code_once;
+  mutable std::unordered_map<std::string, int32_t> code;
 };
 
 extern "C" {
@@ -124,7 +133,6 @@ int ssgpu_dict_create(const char* const* strings, const int32_t* lengths, int64_
   std::sort(d->values.begin(), d->values.end());
   d->values.erase(std::unique(d->values.begin(), d->values.end()), d->values.end());
   if (d->values.size() > (size_t)std::numeric_limits<int32_t>::max()) { delete d; return SSGPU_ERROR_MEMORY_EXCEEDED; }
-  for (size_t i = 0; i < d->values.size(); ++i) d->code[d->values[i]] = (int32_t)i;
   *out = d;
   return SSGPU_OK;
 }
@@ -134,16 +142,49 @@ int32_t ssgpu_dict_size(const ssgpu_dict* d) { return d ? (int32_t)d->values.siz
 int ssgpu_dict_encode(const ssgpu_dict* d, const char* const* strings, const int32_t* lengths, const uint8_t* is_null, int64_t n, int32_t* codes) {
   if (!d || !codes || n < 0 || (n > 0 && (!strings || !lengths))) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
   int rc = SSGPU_OK;
+  const auto& code = d->codes();
   for (int64_t i = 0; i < n; ++i) {
     if (is_null && is_null[i]) { codes[i] = 0; continue; }
-    auto it = d->code.find(std::string(strings[i] ? strings[i] : "", strings[i] ? (size_t)lengths[i] : 0));
-    if (it == d->code.end()) { codes[i] = -1; rc = SSGPU_ERROR_INVALID_ARGUMENT_VALUE; } else codes[i] = it->second;
+    auto it = code.find(std::string(strings[i] ? strings[i] : "", strings[i] ? (size_t)lengths[i] : 0));
+    if (it == code.end()) { codes[i] = -1; rc = SSGPU_ERROR_INVALID_ARGUMENT_VALUE; } else codes[i] = it->second;
   }
   return rc;
 }
 int ssgpu_dict_decode(const ssgpu_dict* d, int32_t code, const char** bytes, int32_t* length) {
   if (!d || code < 0 || (size_t)code >= d->values.size() || !bytes || !length) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
   *bytes = d->values[(size_t)code].data(); *length = (int32_t)d->values[(size_t)code].size();
+  return SSGPU_OK;
+}
+
+// base U strings; remap[c] = the new code of base code c (both dictionaries are sorted, so one merge walk finds them)
+int ssgpu_dict_extend(const ssgpu_dict* base, const char* const* strings, const int32_t* lengths, int64_t n, ssgpu_dict** out, int32_t* remap) {
+  if (!base || !out || n < 0 || (n > 0 && (!strings || !lengths)) || (!remap && !base->values.empty())) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  std::vector<std::string> add;
+  add.reserve((size_t)n);
+  for (int64_t i = 0; i < n; ++i) if (strings[i] && lengths[i] >= 0) add.emplace_back(strings[i], (size_t)lengths[i]);
+  std::sort(add.begin(), add.end());
+  add.erase(std::unique(add.begin(), add.end()), add.end());
+  ssgpu_dict* d = new ssgpu_dict;
+  d->values.reserve(base->values.size() + add.size());
+  std::set_union(base->values.begin(), base->values.end(), add.begin(), add.end(), std::back_inserter(d->values));
+  if (d->values.size() > (size_t)std::numeric_limits<int32_t>::max()) { delete d; return SSGPU_ERROR_MEMORY_EXCEEDED; }
+  size_t j = 0;
+  for (size_t c = 0; c < base->values.size(); ++c) {
+    while (d->values[j] != base->values[c]) ++j;
+    remap[c] = (int32_t)j;
+  }
+  *out = d;
+  return SSGPU_OK;
+}
+
+// internal (runtime.cpp): a dictionary over values that are already sorted and unique -- the distinct strings of a device
+// block in code order, `offsets[n + 1]` into `heap` -- taken as they are
+int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offsets, int64_t n, ssgpu_dict** out) {
+  if (!out || n < 0 || n > (int64_t)std::numeric_limits<int32_t>::max()) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  ssgpu_dict* d = new ssgpu_dict;
+  d->values.reserve((size_t)n);
+  for (int64_t i = 0; i < n; ++i) d->values.emplace_back(heap + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+  *out = d;
   return SSGPU_OK;
 }
 
