@@ -411,8 +411,10 @@ __global__ __launch_bounds__(THREADS) void ssgpu_sort_onesweep_kernel(
 // high half with a neighbour, in runs of 2 or 3) does not need the four low-digit passes: after the stable passes over
 // the high digits the rows of one high half are adjacent and in input order, and sorting each such run by the low half
 // (stable insertion sort, in place, one thread per run) completes the order.  A run longer than SORT_TIE_RUN_MAX raises a
-// flag instead: the host then sorts all digits in LSD order as usual.
+// flag instead: the host then sorts all digits in LSD order as usual (the pairs kernel first looks whether such a run, up to
+// SORT_TIE_ORDERED_MAX rows, is in order as it stands).
 #define SORT_TIE_RUN_MAX 64u
+#define SORT_TIE_ORDERED_MAX 1024u   /* ssgpu_sort_fix_ties_kernel: the longest run it accepts when the run is in order already */
 // A thread looks at SORT_TIE_ROWS consecutive rows (two 16-byte loads and the two neighbours) and fixes the runs that START
 // among them: almost every row is a run of one, so the kernel is a streaming read of the keys.
 #define SORT_TIE_ROWS 4
@@ -421,7 +423,23 @@ __device__ __forceinline__ void sort_fix_run(u64* __restrict__ keys, u32* __rest
   const u64 h = keys[i] >> hi_shift;
   u32 len = 2;
   while (i + len < n && len <= SORT_TIE_RUN_MAX && (keys[i + len] >> hi_shift) == h) ++len;
-  if (len > SORT_TIE_RUN_MAX) { if (*too_long == 0u) atomicExch(too_long, 1u); return; }   // the host sorts all digits instead
+  if (len > SORT_TIE_RUN_MAX) {
+    // A longer run that is in order already needs nothing: copies of ONE key are (the passes are stable, so they are still in
+    // input order).  One thread reads the run in sequence, so this too is bounded (SORT_TIE_ORDERED_MAX; the bound and what
+    // the read costs a sort that falls back anyway are not measured); anything else: the host sorts all digits instead.
+    // Only this (key, row id) form looks: the one-word form (sort_fix_run_compact) still gives up on every run this long.
+    u64 prev = keys[i];
+    u32 m = 1;
+    bool in_order = true;
+    for (; i + m < n && m <= SORT_TIE_ORDERED_MAX; ++m) {
+      const u64 k = keys[i + m];
+      if ((k >> hi_shift) != h) break;
+      if (k < prev) { in_order = false; break; }
+      prev = k;
+    }
+    if (!in_order || m > SORT_TIE_ORDERED_MAX) { if (*too_long == 0u) atomicExch(too_long, 1u); }
+    return;
+  }
   for (u32 a = 1; a < len; ++a) {                             // stable insertion sort of the run by the whole key
     const u64 k = keys[i + a]; const u32 r = HAS_IDX ? idx[i + a] : 0u;
     u32 b = a;
