@@ -412,6 +412,26 @@ int ssgpu_codes_recode(ssgpu_ctx* ctx, const int32_t* src, const uint8_t* is_nul
 int ssgpu_plan_set_dict(ssgpu_plan* plan, const ssgpu_dict* dict);
 const ssgpu_dict* ssgpu_result_column_dict(ssgpu_result* r, int32_t col);
 
+/* Functions that look INSIDE a STRING value (string_expressions.h:46,87-98), as SSGPU_EXPR_OP with the reference's OperatorId:
+ *   OPERATOR_LENGTH = 400         LENGTH(s): STRING -> UINT32, the byte length
+ *   OPERATOR_STRING_OFFSET = 476  STRING_OFFSET(haystack, needle): (STRING, STRING) -> INT32, haystack.find(needle) + 1 -- the 1-based byte
+ *                                 position of the first occurrence, 0 when absent, 1 for an empty needle (string_evaluators.h:69-73)
+ *   OPERATOR_TOLOWER = 420        only as BOTH arguments of a STRING_OFFSET (the form StringContainsCI binds): the search compares through
+ *                                 ascii_tolower (A-Z only; bytes >= 0x80 untouched).  Anywhere else: ERROR_NOT_IMPLEMENTED at bind.
+ * StringContains(h, n) is Less(ConstUInt32(0), StringOffset(h, n)), StringContainsCI the same over TO_LOWER of both.
+ * A value is a code, so f(s) = T[code(s)]: one table T of 4-byte entries per (function, needle, case folding) is built on the device
+ * over the plan's dictionary (string_fn_kernels.hip) before the first run and again after ssgpu_plan_set_dict hands the plan another
+ * dictionary; rows gather from it.  The haystack is any STRING expression; the needle is a STRING constant (a code of the plan's
+ * dictionary) or NULL -- a needle that varies per row is ERROR_NOT_IMPLEMENTED at bind.  A run without a dictionary fails with
+ * ERROR_INVALID_ARGUMENT_VALUE.  Tables share the pipeline's 24 gather slots with the rhs columns of its hash joins.
+ * The cells of a STRING column index the tables as they are: they must be codes of the plan's dictionary (0 for a NULL row), as
+ * ssgpu_dict_encode and the device encoder write them -- a cell outside [0, ssgpu_dict_size) reads outside the table.
+ *
+ * ssgpu_dict_eval computes such a table without a plan: out_host[c] = fn(value c) for the ssgpu_dict_size(d) values of `d`; fn is 400
+ * (needle ignored) or 476; fold_case != 0 compares through ascii_tolower.  SSGPU_ERROR_NO_DEVICE on a bind-only context. */
+int ssgpu_dict_eval(ssgpu_ctx* ctx, const ssgpu_dict* d, int32_t fn, const char* needle, int32_t needle_len, int32_t fold_case,
+                    int32_t* out_host);
+
 /* ---- device-resident Block ----------------------------------------------- */
 /* Layout (base/infrastructure/block.cc:20-36 allocates a buffer per column; so did this library until ABI 9): a block of 32 MiB or
  * more is ONE device allocation, column i's data starting i x (its 2 MiB-rounded size + 512 bytes) into it and the NULL masks

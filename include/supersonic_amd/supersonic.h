@@ -459,6 +459,14 @@ inline const Expression* IsNaN(const Expression* a) { return internal::Op(156, a
 inline const Expression* IsNormal(const Expression* a) { return internal::Op(160, a); }
 inline const Expression* IsOdd(const Expression* a) { return internal::Op(140, a); }
 inline const Expression* IsEven(const Expression* a) { return internal::Op(144, a); }
+// functions of a STRING value (expression/core/string_expressions.h:46,87-98): one table per (function, needle, case folding)
+// over the plan's dictionary, gathered by the value's code.  The needle is a ConstString or Null(STRING); ToLower only as both
+// arguments of a StringOffset -- the form StringContainsCI builds (string_bound_expressions.cc:179-205).
+inline const Expression* Length(const Expression* a) { return internal::Op(400, a); }
+inline const Expression* ToLower(const Expression* a) { return internal::Op(420, a); }
+inline const Expression* StringOffset(const Expression* haystack, const Expression* needle) { return internal::Op(476, haystack, needle); }
+inline const Expression* StringContains(const Expression* haystack, const Expression* needle) { return Less(ConstUint32(0), StringOffset(haystack, needle)); }
+inline const Expression* StringContainsCI(const Expression* haystack, const Expression* needle) { return StringContains(ToLower(haystack), ToLower(needle)); }
 // owning list of expressions (expression/base/expression.h): the arguments of Case / In
 class ExpressionList {
  public:
@@ -1251,6 +1259,7 @@ class BoundExpressionTree {
     int rc = ssgpu_expr_bind(ctx, attrs.data(), static_cast<int32_t>(attrs.size()), exprs_.data(), static_cast<int32_t>(exprs_.size()),
                              expr_args_.data(), static_cast<int32_t>(expr_args_.size()), root_, static_cast<int64_t>(max_row_count_), &plan_);
     if (rc != SSGPU_OK) return rc;
+    if (dict_.d) ssgpu_plan_set_dict(plan_, dict_.d);   // Length / StringOffset read the dictionary's values
     if (memory_limit_ >= 0) ssgpu_plan_set_memory_limit(plan_, memory_limit_);
     schema_ = TupleSchema();
     for (int i = 0; i < ssgpu_plan_attr_count(plan_); ++i) {

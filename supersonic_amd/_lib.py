@@ -140,6 +140,7 @@ SYMBOLS = [
     ("ssgpu_dict_encode", C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), P, C.c_int64, C.POINTER(C.c_int32)]),
     ("ssgpu_dict_decode", C.c_int, [P, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]),
     ("ssgpu_dict_extend", C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int64, C.POINTER(P), C.POINTER(C.c_int32)]),
+    ("ssgpu_dict_eval", C.c_int, [P, P, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("ssgpu_codes_recode", C.c_int, [P, P, P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, P]),
     ("ssgpu_plan_set_memory_limit", C.c_int, [P, C.c_int64]),
     ("ssgpu_plan_set_dict", C.c_int, [P, P]),

@@ -113,6 +113,18 @@ class StringDictionary(object):
     def code_of(self, v):
         return int(self.encode([v], None)[0])
 
+    LENGTH, STRING_OFFSET = 400, 476
+
+    def eval(self, fn, needle=b"", fold_case=False, context=None):
+        """ssgpu_dict_eval: fn of every value, computed on the device -> int32[len(self)].  fn = StringDictionary.LENGTH, or
+        STRING_OFFSET: value.find(needle) + 1 (through ascii_tolower on both sides when fold_case)."""
+        ctx = context or Context.default()
+        nb = _as_bytes(needle)
+        out = np.zeros(len(self), np.int32)
+        ctx.check(self.lib.ssgpu_dict_eval(ctx.handle, self.handle, int(fn), nb, len(nb), 1 if fold_case else 0,
+                                           out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
     def encode(self, data, nulls):
         n = len(data)
         out = np.zeros(n, np.int32)
@@ -690,6 +702,14 @@ def IsNaN(a): return _op(156, a)
 def IsNormal(a): return _op(160, a)
 def IsOdd(a): return _op(140, a)
 def IsEven(a): return _op(144, a)
+
+
+# functions of a STRING value (string_expressions.h:46,87-98): evaluated once per distinct value of the plan's dictionary
+def Length(a): return _op(400, a)
+def ToLower(a): return _op(420, a)                 # only as both arguments of a StringOffset (what StringContainsCI builds)
+def StringOffset(haystack, needle): return _op(476, haystack, needle)
+def StringContains(haystack, needle): return Less(ConstUint32(0), StringOffset(haystack, needle))      # string_bound_expressions.cc:179-189
+def StringContainsCI(haystack, needle): return StringContains(ToLower(haystack), ToLower(needle))      # :193-205
 
 
 class ExpressionList(object):
@@ -1705,6 +1725,7 @@ class BoundExpressionTree(Plan):
         self.ctx.check(self.lib.ssgpu_expr_bind(self.ctx.handle, attrs, schema.attribute_count(), self._keep[2], len(b.exprs),
                                                 self._keep[3], len(b.expr_args), root, self.max_row_count, C.byref(h)))
         self._adopt(h)
+        self.lib.ssgpu_plan_set_dict(h, self.strings.handle)      # LENGTH / STRING_OFFSET read the dictionary's values
         if self.allocator is not None:
             self.set_buffer_allocator(self.allocator)
 

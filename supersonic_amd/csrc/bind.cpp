@@ -7,6 +7,7 @@
 //   logic / IF / ISNULL supersonic/expression/core/elementary_bound_expressions.cc:1084-1430
 //   constant folding    supersonic/expression/infrastructure/basic_bound_expression.cc:57-92
 //   projectors          supersonic/base/infrastructure/projector.cc:95-270
+//   string functions    supersonic/expression/core/string_bound_expressions.cc:170-205, expression_traits.h:642-694,1592-1605
 #include "engine.h"
 
 #include <math.h>
@@ -29,6 +30,7 @@ enum {
   OP_ASIN = 812, OP_ACOS = 816, OP_ATAN = 820, OP_ATAN2 = 824, OP_SINH = 828, OP_COSH = 832, OP_TANH = 836, OP_ASINH = 840,
   OP_ACOSH = 844, OP_ATANH = 848,
   OP_SQRT_QUIET = 333, OP_SQRT_NULLING = 334, OP_SQRT_SIGNALING = 335, OP_CEIL = 342, OP_FLOOR = 346, OP_ABS = 360,
+  OP_LENGTH = 400, OP_TOLOWER = 420, OP_STRING_OFFSET = 476,
   OP_CASE = 200, OP_IF = 204, OP_IN = 208, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265
 };
 
@@ -716,6 +718,41 @@ static Status bind_operator(const ssgpu_expr& x, std::vector<BExprP> args, int d
       *out = fold(make_op(op, SSGPU_BOOL, args[0]->nullable, std::string(op == OP_IS_ODD ? "IS_ODD(" : "IS_EVEN(") + args[0]->name + ")", {args[0]}, depth));
       return Status::OK();
     }
+    // ---- functions of a STRING value: evaluated per distinct value of the plan's dictionary and gathered by the code
+    // (lower.cpp, string_fn_kernels.hip).  No promotion applies (supports_promotions = false): any other type is a mismatch.
+    case OP_LENGTH:
+      SS_RETURN_IF_ERROR(need(1));
+      if (args[0]->dtype != SSGPU_STRING)
+        return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("LENGTH needs a STRING argument, got ") + dtype_name(args[0]->dtype) + " in " + args[0]->name);
+      *out = make_op(op, SSGPU_UINT32, args[0]->nullable, "LENGTH(" + args[0]->name + ")", {args[0]}, depth);
+      return Status::OK();
+    case OP_TOLOWER:
+      // a marker, never a value: bind_expression lets it through only as an argument of STRING_OFFSET, which takes it apart
+      SS_RETURN_IF_ERROR(need(1));
+      if (args[0]->dtype != SSGPU_STRING)
+        return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("TO_LOWER needs a STRING argument, got ") + dtype_name(args[0]->dtype) + " in " + args[0]->name);
+      *out = make_op(op, SSGPU_STRING, args[0]->nullable, "TO_LOWER(" + args[0]->name + ")", {args[0]}, depth);
+      return Status::OK();
+    case OP_STRING_OFFSET: {
+      SS_RETURN_IF_ERROR(need(2));
+      auto lowered = [](const BExprP& e) { return e->kind == BExpr::OP && e->op == OP_TOLOWER; };
+      const bool fold = lowered(args[0]) && lowered(args[1]);
+      if (lowered(args[0]) != lowered(args[1]))
+        return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "TO_LOWER is implemented only under BOTH arguments of STRING_OFFSET (StringContainsCI), not under one: " +
+                                                              std::string("STRING_OFFSET(") + args[0]->name + ", " + args[1]->name + ")");
+      const BExprP hay = fold ? args[0]->args[0] : args[0], needle = fold ? args[1]->args[0] : args[1];
+      for (const BExprP& a : {hay, needle})
+        if (a->dtype != SSGPU_STRING)
+          return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("STRING_OFFSET needs STRING arguments, got ") + dtype_name(a->dtype) + " in " + a->name);
+      if (!is_constant(needle))
+        return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "STRING_OFFSET: the needle must be a STRING constant or NULL (one table per needle is built over the "
+                                                          "dictionary); a needle that varies per row (" + needle->name + ") is outside the device hot path");
+      // nothing folds here: a STRING constant is a code, and the dictionary arrives after the plan is made (ssgpu_plan_set_dict)
+      BExprP e = make_op(op, SSGPU_INT32, hay->nullable || needle->nullable, "STRING_OFFSET(" + args[0]->name + ", " + args[1]->name + ")", {hay, needle}, depth);
+      e->bits = fold ? 1 : 0;
+      *out = e;
+      return Status::OK();
+    }
     case OP_CASE: {
       // CASE arg0 WHEN arg2 THEN arg3 ... ELSE arg1 (BoundCase, elementary_bound_expressions.cc:1297-1356).
       // Bound as a chain of plain IFs over equality tests, which has exactly the reference's
@@ -822,7 +859,13 @@ static Status bind_operator(const ssgpu_expr& x, std::vector<BExprP> args, int d
                        "OperatorId " + std::to_string(op) + " is outside the device hot path (SURVEY 8: math/date/string/regexp)");
 }
 
+// TO_LOWER yields a STRING that exists in no dictionary, so it binds only where STRING_OFFSET takes it apart again
+// (`under_offset`: the expression is a direct argument of one)
+static Status bind_expression_at(const PlanDesc& d, int idx, const Schema& schema, int depth, bool under_offset, std::vector<BExprP>* out);
 Status bind_expression(const PlanDesc& d, int idx, const Schema& schema, int depth, std::vector<BExprP>* out) {
+  return bind_expression_at(d, idx, schema, depth, false, out);
+}
+static Status bind_expression_at(const PlanDesc& d, int idx, const Schema& schema, int depth, bool under_offset, std::vector<BExprP>* out) {
   if (idx < 0 || idx >= (int)d.exprs.size()) return Status::Error(SSGPU_ERROR_INVALID_ARGUMENT_VALUE, "bad expression index");
   const ssgpu_expr& x = d.exprs[idx];
   auto input = [&](int pos) {
@@ -885,10 +928,13 @@ Status bind_expression(const PlanDesc& d, int idx, const Schema& schema, int dep
       return Status::OK();
     }
     case SSGPU_EXPR_OP: {
+      if (x.op == OP_TOLOWER && !under_offset)
+        return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "TO_LOWER is implemented only as both arguments of STRING_OFFSET (StringContainsCI): a lowered STRING "
+                                                          "is a value the plan's dictionary does not hold");
       std::vector<BExprP> args;
       for (int i = 0; i < x.nargs; ++i) {
         std::vector<BExprP> child;
-        SS_RETURN_IF_ERROR(bind_expression(d, d.expr_args[x.first_arg + i], schema, depth, &child));
+        SS_RETURN_IF_ERROR(bind_expression_at(d, d.expr_args[x.first_arg + i], schema, depth, x.op == OP_STRING_OFFSET, &child));
         if (child.size() != 1)
           return Status::Error(SSGPU_ERROR_ATTRIBUTE_COUNT_MISMATCH, "operator arguments must have exactly one attribute");
         args.push_back(child[0]);

@@ -20,6 +20,9 @@
 // seams.cpp: a dictionary over values already sorted and unique (`offsets[n + 1]` into `heap`), taken without sorting again --
 // how the distinct strings a device block's STRING columns were encoded with come back to the host
 extern "C" int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offsets, int64_t n, ssgpu_dict** out);
+// ... and the other way: a dictionary's values packed for the device (`offsets[n + 1]`, `heap` of ssgpu_dict_heap_bytes bytes)
+extern "C" uint64_t ssgpu_dict_heap_bytes(const ssgpu_dict* d);
+extern "C" void ssgpu_dict_pack(const ssgpu_dict* d, uint64_t* offsets, char* heap);
 
 namespace ssgpu {
 
@@ -100,7 +103,11 @@ struct JoinSpec {
   bool wide = false;                     // the packed key takes two 64-bit words (JOIN_PROBE_WIDE)
   int depth = 0;                         // number of Filters below the join: rows their selection dropped are not probed
 };
-struct JoinGather { int join_id; int rhs_col; bool is_null_mask; };  // slot i of VmParams.join_cols
+// slot i of VmParams.join_cols: a column (or NULL mask) of a join's rhs table, or -- join_id == JOIN_GATHER_DICT_TABLE -- a table
+// over the plan's STRING dictionary, indexed by a code: table[c] = fn(value c) (string_fn_kernels.hip), fn = 400 LENGTH,
+// 476 STRING_OFFSET of the value whose code is `needle_code`, compared through ascii_tolower when `fold`
+struct JoinGather { int join_id; int rhs_col; bool is_null_mask; int fn = 0; int32_t needle_code = 0; bool fold = false; };
+enum { JOIN_GATHER_DICT_TABLE = -2 };
 enum { JOIN_GATHER_RUN_START = -1, JOIN_GATHER_RUN_COUNT = -2 };   // rhs_col of a multi join's per-key run arrays
 
 // Lowered instruction over virtual registers.  A register is an LDS array of

@@ -333,6 +333,12 @@ hipError_t ssgpu_launch_str_gather(const uint8_t* bytes, const uint64_t* d_off, 
                                    uint8_t* out, hipStream_t s);
 hipError_t ssgpu_launch_str_recode(const int32_t* src, const uint8_t* nulls, const int32_t* remap, int32_t n_remap, uint64_t n, int32_t* dst,
                                    hipStream_t s);
+// functions of the dictionary's values (string_fn_kernels.hip): table[c] = fn(value c) for the packed dictionary `offs[n + 1]` / `heap`;
+// fn = 400 LENGTH, 476 STRING_OFFSET of `needle` (fold: through ascii_tolower).  The heap's allocation extends STRFN_HEAP_PAD bytes
+// past offs[n] (the kernel reads it in aligned 16-byte words) and starts 16-byte aligned.
+#define STRFN_HEAP_PAD 32
+hipError_t ssgpu_launch_str_fn(const uint8_t* heap, const uint64_t* offs, uint64_t n, int fn, const uint8_t* needle, uint32_t needle_len,
+                               int fold, uint32_t* table, hipStream_t s);
 hipError_t ssgpu_launch_sort_unkey(void* out, const uint64_t* keys, uint32_t width, int kind, int descending, uint64_t n, hipStream_t s);
 hipError_t ssgpu_launch_sort_gather(void* out, uint8_t* out_nulls, const void* col, const uint8_t* nulls, uint32_t width,
                                     const uint32_t* idx, uint64_t n, hipStream_t s);

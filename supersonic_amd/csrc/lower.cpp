@@ -34,7 +34,7 @@ enum {
   OP_AND_NOT = 48, OP_NOT = 52, OP_XOR = 56, OP_BITWISE_AND = 60, OP_BITWISE_OR = 64,
   OP_BITWISE_NOT = 68, OP_BITWISE_XOR = 72, OP_SHIFT_LEFT = 76, OP_SHIFT_RIGHT = 80,
   OP_BITWISE_ANDNOT = 84, OP_EQUAL = 100, OP_NOT_EQUAL = 104, OP_LESS = 116, OP_LESS_OR_EQUAL = 120,
-  OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265
+  OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265, OP_LENGTH = 400, OP_STRING_OFFSET = 476
 };
 
 // machine type classes
@@ -138,6 +138,17 @@ class Emitter {
     P->gathers.push_back(g);
     return (int)P->gathers.size() - 1;
   }
+  // a table over the plan's STRING dictionary (string_fn_kernels.hip): shares the join gathers' slots; equal
+  // (function, needle, fold) nodes share one table
+  int table_slot(int fn, int32_t needle_code, bool fold) {
+    for (size_t i = 0; i < P->gathers.size(); ++i) {
+      const JoinGather& t = P->gathers[i];
+      if (t.join_id == JOIN_GATHER_DICT_TABLE && t.fn == fn && t.needle_code == needle_code && t.fold == fold) return (int)i;
+    }
+    JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.fn = fn; g.needle_code = needle_code; g.fold = fold;
+    P->gathers.push_back(g);
+    return (int)P->gathers.size() - 1;
+  }
 
   // join_index: the stage's filter chain and whether later filters may be evaluated ahead of a probe (emit_filters sets both)
   const std::vector<BExprP>* filters_ = nullptr;
@@ -210,7 +221,9 @@ std::string Emitter::key_of(const BExprP& e) {
     case BExpr::JOINCNT: s << "JC" << e->join_id; break;
     case BExpr::ROWID: s << "R"; break;
     default:
-      s << (e->kind == BExpr::CAST ? "K" : "O") << e->op << ":" << e->dtype << ":" << e->filter_depth << "(";
+      s << (e->kind == BExpr::CAST ? "K" : "O") << e->op << ":" << e->dtype << ":" << e->filter_depth;
+      if (e->kind == BExpr::OP && e->op == OP_STRING_OFFSET) s << (e->bits ? "ci" : "cs");   // BExpr::bits: compared through ascii_tolower
+      s << "(";
       for (auto& a : e->args) s << key_of(a) << ",";
       s << ")";
   }
@@ -549,6 +562,18 @@ Status Emitter::value(const BExprP& e, Val* out) {
           }
           v.reg = unop(VM_SQRT_F64, a[0], v.width);
           v.null = base_null;
+        } break;
+        case OP_LENGTH: case OP_STRING_OFFSET: {
+          // f(s) = T[code(s)]: the table is built once per distinct value before the first run (runtime.cpp: dictionary tables);
+          // the NULL mask is the haystack's own -- T has no NULLs and a code is never VM_NONE (NULL rows and the rows past the end of
+          // the last tile carry code 0, and T always has an entry 0)
+          const bool offset = e->op == OP_STRING_OFFSET;
+          if (offset && e->args[1]->kind == BExpr::NULLCONST) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // NULL needle
+          const int code = materialize(a[0]);
+          const int slot = table_slot(offset ? OP_STRING_OFFSET : OP_LENGTH, offset ? (int32_t)(uint32_t)e->args[1]->bits : 0, offset && e->bits != 0);
+          v.reg = new_reg(4);
+          LInstr& i = emit(VM_GATHER_32); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot;
+          v.null = a[0].null;
         } break;
         case OP_NEGATE: v.reg = unop(pick(mt, VM_NEG_I32, VM_NEG_I32, VM_NEG_I64, VM_NEG_I64, VM_NEG_F32, VM_NEG_F64), a[0], v.width); v.null = a[0].null; break;
         case OP_BITWISE_AND: v.reg = binop(v.width == 4 ? VM_BAND_32 : VM_BAND_64, a[0], a[1], v.width); v.null = or_null(a[0].null, a[1].null); break;
@@ -2359,7 +2384,8 @@ Status lower_plan(const PlanDesc& d, std::vector<Stage>* stages, Schema* result_
   for (auto& st : *stages)
     for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
       if (pr->gathers.size() > VM_MAX_JOIN_COLS)
-        return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "too many rhs columns gathered by the hash joins of one pipeline");
+        return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "too many rhs columns gathered by the hash joins of one pipeline (with its tables over the STRING dictionary: " +
+                                                              std::to_string(pr->gathers.size()) + " of " + std::to_string(VM_MAX_JOIN_COLS) + " slots)");
   *result_schema = stages->back().out_schema;
   for (auto& cc : stages->back().concat) { (*result_schema)[cc.out_col].dtype = SSGPU_STRING; (*result_schema)[cc.out_col].nullable = true; }   // (out_schema keeps the device's UINT64 count)
   for (size_t i = 0; i < stages->size(); ++i) {

@@ -8,6 +8,8 @@
 
 #include <atomic>
 #include <map>
+#include <tuple>
+#include <set>
 #include <mutex>
 #include <stdio.h>
 #include <string.h>
@@ -108,6 +110,7 @@ struct QuotaScope { MemQuota* saved; explicit QuotaScope(MemQuota* q) : saved(g_
 
 // process-wide accounting of what the library holds (ssgpu_memory_stats): the per-process measure behind the
 // "repeated runs do not grow memory" contract (expression_test_helper.cc:213-245 watches its allocator the same way)
+static std::atomic<uint64_t> g_dict_gen{0};   // stamps of ssgpu_plan_set_dict calls (ssgpu_plan::dict_gen)
 static std::atomic<long long> g_dev_bytes{0}, g_pinned_bytes{0}, g_live_plans{0}, g_live_blocks{0}, g_events{0};
 
 // A small pool of device blocks between plans.  The reference's usage model is a cursor per query, drained once
@@ -342,6 +345,9 @@ struct StageExec {
   uint32_t steady_bypass = 0;   // direct shape: rows that bypassed the LDS table in the last synchronous run
 };
 
+// A STRING dictionary packed for the device: `offs[n + 1]` into one byte heap (STRFN_HEAP_PAD zero bytes behind it)
+struct DictDevice { DevBuf offs, heap; uint64_t n = 0; };
+
 struct ssgpu_result {
   ssgpu_plan* plan = nullptr;
   std::vector<PinnedBuf> host_data, host_nulls;
@@ -387,6 +393,16 @@ struct ssgpu_plan {
   bool deferred = false;        // some stage's run feedback has not been looked at yet (settle_plan)
   bool nan_seen = false;        // the last run met a NaN in a floating MIN / MAX (check_error_flags)
   const ssgpu_dict* dict = nullptr;   // the plan's STRING dictionary (ssgpu_plan_set_dict): CONCAT prints STRING inputs through it
+  // Tables over that dictionary (Program::gathers of JOIN_GATHER_DICT_TABLE; string_fn_kernels.hip): the dictionary packed and uploaded
+  // once, one table of 4-byte entries per (function, needle code, fold).  Dictionaries are immutable, so the tables are built lazily
+  // before the first run that needs them and again when the plan is handed another dictionary (dict_gen: the stamp of the
+  // ssgpu_plan_set_dict call, so that a new dictionary at a freed one's address is not mistaken for it); freed with the plan.
+  uint64_t dict_gen = 0;
+  struct DictTables {
+    bool built = false; uint64_t built_gen = 0; const ssgpu_dict* built_for = nullptr;
+    DictDevice dev; DevBuf needle;
+    std::map<std::tuple<int, int32_t, bool>, DevBuf> tables;
+  } dict_tables;
   std::vector<ssgpu_column> last_cols; int64_t last_base = 0; bool last_partial = false;   // the last run's input (a deferred overflow repeats it)
   // ssgpu_plan_run_host: two alternating sets of device columns the host rows are staged through, and the chunks' partial states
   std::vector<DevBuf> host_stage_data[2], host_stage_nulls[2];
@@ -1071,7 +1087,25 @@ int ssgpu_plan_attr(const ssgpu_plan* p, int32_t i, ssgpu_attr* out) {
   out->nullable = p->result_schema[i].nullable ? 1 : 0;
   return SSGPU_OK;
 }
-const char* ssgpu_plan_describe(ssgpu_plan* p) { return p ? p->describe.c_str() : ""; }
+const char* ssgpu_plan_describe(ssgpu_plan* p) {
+  if (!p) return "";
+  // one line per table over the STRING dictionary: function, needle (its length once the dictionary is known), case folding
+  std::set<std::tuple<int, int32_t, bool>> seen;
+  std::string lines;
+  for (auto& st : p->stages)
+    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
+      for (auto& g : pr->gathers) {
+        if (g.join_id != JOIN_GATHER_DICT_TABLE || !seen.insert(std::make_tuple(g.fn, g.needle_code, g.fold)).second) continue;
+        if (g.fn != 476) { lines += "dictionary table: LENGTH\n"; continue; }
+        const char* bytes = nullptr; int32_t len = 0;
+        lines += "dictionary table: STRING_OFFSET needle code " + std::to_string(g.needle_code) +
+                 (p->dict && ssgpu_dict_decode(p->dict, g.needle_code, &bytes, &len) == SSGPU_OK ? " length " + std::to_string(len) : std::string(" length unknown (no dictionary yet)")) +
+                 " fold " + (g.fold ? "1" : "0") + "\n";
+      }
+  if (lines.empty()) return p->describe.c_str();
+  p->describe_full = p->describe + lines;
+  return p->describe_full.c_str();
+}
 
 int ssgpu_plan_program(const ssgpu_plan* cp, int32_t stage, const void** instrs, int32_t* n, int32_t* bytes) {
   ssgpu_plan* p = const_cast<ssgpu_plan*>(cp);
@@ -1257,10 +1291,76 @@ int build_joins(ssgpu_plan* p, Stage& st, StageExec& ex) {
   }
   return SSGPU_OK;
 }
+// ---- tables over the STRING dictionary (string_fn_kernels.hip) ------------------------------------------------------
+int dict_upload(ssgpu_ctx* c, const ssgpu_dict* d, DictDevice* out) {
+  const uint64_t n = (uint64_t)ssgpu_dict_size(d), hb = ssgpu_dict_heap_bytes(d);
+  std::vector<uint64_t> offs(n + 1);
+  std::vector<char> heap(hb + 1);
+  ssgpu_dict_pack(d, offs.data(), heap.data());
+  HIP_TRY(c, out->offs.ensure((n + 1) * 8));
+  HIP_TRY(c, out->heap.ensure(hb + STRFN_HEAP_PAD));
+  HIP_TRY(c, hipMemcpyAsync(out->offs.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (hb) HIP_TRY(c, hipMemcpyAsync(out->heap.p, heap.data(), hb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(static_cast<char*>(out->heap.p) + hb, 0, STRFN_HEAP_PAD, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host copies above go out of scope)
+  out->n = n;
+  return SSGPU_OK;
+}
+// table[c] = fn(value c); an empty dictionary gets ONE entry: NULL rows carry code 0 and the gather still reads table[0]
+int dict_table_build(ssgpu_ctx* c, const DictDevice& D, int fn, const char* needle, uint32_t nlen, bool fold, DevBuf* needle_dev, DevBuf* table) {
+  HIP_TRY(c, table->ensure((size_t)std::max<uint64_t>(D.n, 1) * 4));
+  if (D.n == 0) { HIP_TRY(c, hipMemsetAsync(table->p, 0, 4, c->stream)); return SSGPU_OK; }
+  HIP_TRY(c, needle_dev->ensure(std::max<uint32_t>(nlen, 1)));
+  if (fn == 476 && nlen) HIP_TRY(c, hipMemcpyAsync(needle_dev->p, needle, nlen, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, ssgpu_launch_str_fn(D.heap.as<const uint8_t>(), D.offs.as<const uint64_t>(), D.n, fn, needle_dev->as<const uint8_t>(), fn == 476 ? nlen : 0u,
+                                 fold ? 1 : 0, table->as<uint32_t>(), c->stream));
+  return SSGPU_OK;
+}
+static bool plan_has_dict_tables(const ssgpu_plan* p) {
+  for (auto& st : p->stages)
+    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
+      for (auto& g : pr->gathers) if (g.join_id == JOIN_GATHER_DICT_TABLE) return true;
+  return false;
+}
+// before a run: every table the plan's programs gather from exists and belongs to the plan's current dictionary
+int ensure_dict_tables(ssgpu_plan* p) {
+  if (!plan_has_dict_tables(p)) return SSGPU_OK;
+  ssgpu_ctx* c = p->ctx;
+  if (!p->dict) { c->err = "LENGTH / STRING_OFFSET of a STRING value need the plan's dictionary (ssgpu_plan_set_dict)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  ssgpu_plan::DictTables& T = p->dict_tables;
+  if (T.built && T.built_for == p->dict && T.built_gen == p->dict_gen) return SSGPU_OK;
+  T.built = false;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (an earlier run may still read the tables that are replaced now)
+  int rc = dict_upload(c, p->dict, &T.dev);
+  if (rc != SSGPU_OK) return rc;
+  const int32_t n = ssgpu_dict_size(p->dict);
+  for (auto& st : p->stages)
+    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
+      for (auto& g : pr->gathers) {
+        if (g.join_id != JOIN_GATHER_DICT_TABLE) continue;
+        const char* needle = ""; int32_t nlen = 0;
+        if (g.fn == 476 && ssgpu_dict_decode(p->dict, g.needle_code, &needle, &nlen) != SSGPU_OK) {
+          c->err = "STRING_OFFSET: the needle's code " + std::to_string(g.needle_code) + " is outside the plan's dictionary of " + std::to_string(n) + " values (ssgpu_plan_set_dict)";
+          return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+        }
+        rc = dict_table_build(c, T.dev, g.fn, needle, (uint32_t)nlen, g.fold, &T.needle, &T.tables[std::make_tuple(g.fn, g.needle_code, g.fold)]);
+        if (rc != SSGPU_OK) return rc;
+        p->counters.n_launches += 1;
+      }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  T.built = true; T.built_for = p->dict; T.built_gen = p->dict_gen;
+  return SSGPU_OK;
+}
+
 void apply_joins(const ssgpu_plan* p, const StageExec& ex, const Program& prog, VmParams* P) {
   for (size_t j = 0; j < ex.vm_joins.size() && j < VM_MAX_JOINS; ++j) P->join[j] = ex.vm_joins[j];
   for (size_t g = 0; g < prog.gathers.size() && g < VM_MAX_JOIN_COLS; ++g) {
     const JoinGather& jg = prog.gathers[g];
+    if (jg.join_id == JOIN_GATHER_DICT_TABLE) {   // a table over the STRING dictionary, indexed by a code (ensure_dict_tables)
+      auto it = p->dict_tables.tables.find(std::make_tuple(jg.fn, jg.needle_code, jg.fold));
+      P->join_cols[g].data = it != p->dict_tables.tables.end() ? it->second.p : nullptr; P->join_cols[g].is_null = nullptr;
+      continue;
+    }
     if (jg.rhs_col < 0) {   // the per-key run arrays of a NOT_UNIQUE join, indexed by the probed slot
       const DevBuf& b = jg.rhs_col == JOIN_GATHER_RUN_START ? ex.jstarts[jg.join_id] : ex.jcounts[jg.join_id];
       P->join_cols[g].data = b.p; P->join_cols[g].is_null = nullptr;
@@ -3069,6 +3169,7 @@ int run_plan(ssgpu_plan* p, const ssgpu_column* cols, int32_t n_cols, int64_t ro
   { const int orc = order_after_uploads(c); if (orc != SSGPU_OK) return orc; }
   // blocks are staged on the copy stream: kernels must wait for those copies
   memset(&p->counters, 0, sizeof(p->counters));
+  { const int trc = ensure_dict_tables(p); if (trc != SSGPU_OK) return trc; }
   p->counters.rows_in = rows;
   p->result.fetched.assign(p->result.fetched.size(), false);
   for (ssgpu_dict*& cd : p->result.concat_dicts) { if (cd) ssgpu_dict_destroy(cd); cd = nullptr; }
@@ -3414,7 +3515,7 @@ int ssgpu_expr_evaluate_skip(ssgpu_plan* bound, const ssgpu_column* cols, int32_
     bound->skip_plan = q;
   }
   ssgpu_plan* q = bound->skip_plan;
-  q->dict = bound->dict; q->quota.limit = bound->quota.limit;
+  q->dict = bound->dict; q->dict_gen = bound->dict_gen; q->quota.limit = bound->quota.limit;
   if (n_cols != (int)D.input_schema.size()) { c->err = "column count does not match the plan's input schema"; return SSGPU_ERROR_ATTRIBUTE_COUNT_MISMATCH; }
   if (!c || c->device < 0) { if (c) c->err = "no gfx950 device bound to this context (bind-only context)"; return SSGPU_ERROR_NO_DEVICE; }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -3674,7 +3775,7 @@ static int stream_job_prepare(ssgpu_plan* p, int* kind_out, bool for_run = true)
   J.acc_rows = 0;
   for (ssgpu_plan* q : {J.head, J.tail}) {
     if (!q || q == p) continue;
-    q->aux_cols = p->aux_cols; q->aux_rows = p->aux_rows; q->dict = p->dict; q->quota.limit = p->quota.limit;
+    q->aux_cols = p->aux_cols; q->aux_rows = p->aux_rows; q->dict = p->dict; q->dict_gen = p->dict_gen; q->quota.limit = p->quota.limit;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   stream_job_reset_out(J.head);
@@ -4381,6 +4482,37 @@ extern "C" {
 int ssgpu_plan_set_dict(ssgpu_plan* p, const ssgpu_dict* dict) {
   if (!p) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
   p->dict = dict;
+  p->dict_gen = g_dict_gen.fetch_add(1) + 1;   // tables over the previous dictionary are rebuilt before the next run (ensure_dict_tables)
+  return SSGPU_OK;
+}
+
+// T[c] = fn(value c) for every value of `d`, on the device (string_fn_kernels.hip) -- the tables a plan gathers LENGTH / STRING_OFFSET
+// from, without a plan.  fn: 400 LENGTH (needle ignored), 476 STRING_OFFSET.  out_host: ssgpu_dict_size(d) entries.
+int ssgpu_dict_eval(ssgpu_ctx* c, const ssgpu_dict* d, int32_t fn, const char* needle, int32_t needle_len, int32_t fold_case, int32_t* out_host) {
+  if (!c) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  if (!d || (fn != 400 && fn != 476) || needle_len < 0 || (needle_len > 0 && !needle)) { c->err = "ssgpu_dict_eval: a dictionary, fn 400 (LENGTH) or 476 (STRING_OFFSET) and the needle's bytes"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  if (c->device < 0) { c->err = "no gfx950 device bound to this context (bind-only context)"; return SSGPU_ERROR_NO_DEVICE; }
+  const int32_t n = ssgpu_dict_size(d);
+  if (n > 0 && !out_host) { c->err = "ssgpu_dict_eval: no result buffer"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  DictDevice D; DevBuf needle_dev, table;
+  struct Events { hipEvent_t e[3] = {nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } events;
+  hipEvent_t* ev = events.e;
+  const bool timed = c->debug_timing != 0;   // development: upload and kernel times on stderr (tools/string_fn_bench.py)
+  if (timed) { for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventCreate(&ev[i])); HIP_TRY(c, hipEventRecord(ev[0], c->stream)); }
+  int rc = dict_upload(c, d, &D);
+  if (rc != SSGPU_OK) return rc;
+  if (timed) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+  rc = dict_table_build(c, D, fn, needle, (uint32_t)needle_len, fold_case != 0, &needle_dev, &table);
+  if (rc != SSGPU_OK) return rc;
+  if (timed) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
+  if (n > 0) HIP_TRY(c, hipMemcpyAsync(out_host, table.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (timed) {
+    float up = 0, k = 0;
+    (void)hipEventElapsedTime(&up, ev[0], ev[1]); (void)hipEventElapsedTime(&k, ev[1], ev[2]);
+    fprintf(stderr, "[ssgpu dict_eval] values %d upload_ms %.4f kernel_ms %.4f\n", n, up, k);
+  }
   return SSGPU_OK;
 }
 const ssgpu_dict* ssgpu_result_column_dict(ssgpu_result* r, int32_t i) {

@@ -188,4 +188,21 @@ int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offsets, int64_t 
   return SSGPU_OK;
 }
 
+// internal (runtime.cpp): the dictionary packed for the device -- `offsets[n + 1]` into one byte heap of ssgpu_dict_heap_bytes
+uint64_t ssgpu_dict_heap_bytes(const ssgpu_dict* d) {
+  uint64_t total = 0;
+  if (d) for (const std::string& v : d->values) total += v.size();
+  return total;
+}
+void ssgpu_dict_pack(const ssgpu_dict* d, uint64_t* offsets, char* heap) {
+  uint64_t at = 0;
+  const size_t n = d ? d->values.size() : 0;
+  for (size_t i = 0; i < n; ++i) {
+    offsets[i] = at;
+    memcpy(heap + at, d->values[i].data(), d->values[i].size());
+    at += d->values[i].size();
+  }
+  offsets[n] = at;
+}
+
 }  // extern "C"
