@@ -432,6 +432,51 @@ const ssgpu_dict* ssgpu_result_column_dict(ssgpu_result* r, int32_t col);
 int ssgpu_dict_eval(ssgpu_ctx* ctx, const ssgpu_dict* d, int32_t fn, const char* needle, int32_t needle_len, int32_t fold_case,
                     int32_t* out_host);
 
+/* Functions whose RESULT is a STRING (string_expressions.h:30-44,52-58; string_evaluators.h:41-67,96-132), as SSGPU_EXPR_OP:
+ *   OPERATOR_LTRIM = 404, OPERATOR_RTRIM = 408, OPERATOR_TRIM = 412   strip byte 0x20 only ('\t', '\n' stay)
+ *   OPERATOR_TOUPPER = 416                                           ascii_toupper: a-z only, bytes >= 0x80 and 0x00 untouched
+ *   OPERATOR_SUBSTRING_SIGNALING = 427, 3 arguments SUBSTRING(x, pos, len): len = max(len, 0); pos > 0 counts from 1, pos <= 0 from the
+ *                                  end (pos += length, clamped at 0); the value is substr(pos, len) with StringPiece's clamping, so
+ *                                  SUBSTRING(s, 0, n) is "";  2 arguments SUBSTRING(x, pos) (TrailingSubstring): to the end of x.
+ * x is any STRING expression (anything else: ERROR_ATTRIBUTE_TYPE_MISMATCH); pos / len are integer CONSTANTS of any integer type, taken as
+ * INT64 (FLOAT / DOUBLE: type mismatch; a value that varies per row: ERROR_NOT_IMPLEMENTED at bind -- one table per (function, pos,
+ * len) is the mechanism); a NULL pos / len gives an all-NULL result and needs no table.  The result is STRING, NULL iff an argument is.
+ * TO_LOWER (420) as a value is still refused at bind (the kernels take the fold direction as a parameter: lifting it is a binder change).
+ *
+ * THE CLOSED DICTIONARY.  The result of such a node is again a code of the plan's one dictionary, so everything downstream -- comparison,
+ * sort, group / join keys, MIN / MAX, CONCAT, fetch and decode, LENGTH / STRING_OFFSET on top -- works on it unchanged, and the node itself
+ * is GATHER_32 by the code register from a table T[code(v)] = code(f(v)).  For that the dictionary must hold every value the plan's
+ * producer nodes can make.  ssgpu_plan_string_steps gives the plan's STEP LIST: its producer nodes (those with a NULL pos / len left out) in
+ * evaluation order -- stage after stage, program after program of a stage (main, counting pass, partition scatter), arguments before the node
+ * that uses them; a (fn, pos, len) key that occurs twice is listed twice.  Returns the count and writes at most `cap` records; works on a
+ * bind-only context.  ssgpu_dict_close closes `base` under a step list on the device (string_map_kernels.hip + the encoder of
+ * string_dict_kernels.hip): D_0 = base, D_k = D_(k-1) U f_k(D_(k-1)); every value that can reach the k-th node lies in D_(k-1), since the
+ * other STRING expressions (columns, constants, IF / CASE / IFNULL, join gathers) only select among existing values.  *out is D_final as a
+ * new dictionary (the caller destroys it), remap[c] (ssgpu_dict_size(base) entries) the new code of base code c.  The result remembers its
+ * step list and one table per step, indexed by ITS codes: T_k[code(v)] = code(f_k(v)) for every v of D_(k-1), and 0 for every other
+ * value -- every entry of every table lies in [0, ssgpu_dict_size), so a gather by any code read from a column, a NULL row's 0 or another
+ * table stays inside the next table.  n == 0: a copy of base, identity remap.  The result depends only on base's SET of values and the step
+ * list: ranks that close equal dictionaries under equal lists get equal codes.  SSGPU_ERROR_NO_DEVICE on a bind-only context.
+ * ssgpu_dict_step_table copies T_k (ssgpu_dict_size entries) out, for tests and tools; ERROR_INVALID_ARGUMENT_VALUE when `closed` has no step k.
+ * ssgpu_dict_extend of a closed dictionary gives an ordinary one (no steps).
+ *
+ * A plan with producer nodes RUNS only on a dictionary closed under a list that has the plan's own step list as a SUBSEQUENCE (a later
+ * step's domain contains every earlier one, so skipping steps is sound; the head / tail plans of chunked execution, the NaN-exact repeat
+ * and the skip form of a bound expression hold subsets of the plan's nodes): ssgpu_plan_set_dict(closed), and STRING constants of the plan
+ * description must be codes of the CLOSED dictionary, so a caller creates the plan, asks for its steps, closes its dictionary, emits the
+ * description again and creates the plan anew.  The run uploads the dictionary's own tables -- nodes with an equal key share the table of the
+ * LAST step with that key, whose domain is the largest -- and computes nothing.  Any other dictionary (none, unclosed, closed under another
+ * list) fails the run with ERROR_INVALID_ARGUMENT_VALUE naming ssgpu_dict_close: a run never reads a table that is not its own. */
+typedef struct ssgpu_string_step {
+  int32_t fn;       /* 404 LTRIM, 408 RTRIM, 412 TRIM, 416 TO_UPPER, 427 SUBSTRING (ssgpu_dict_close also takes 420 TO_LOWER) */
+  int32_t has_len;  /* SUBSTRING: 1 = the 3-argument form */
+  int64_t pos;      /* SUBSTRING only, else 0 */
+  int64_t len;      /* SUBSTRING with has_len only, else 0 */
+} ssgpu_string_step;
+int32_t ssgpu_plan_string_steps(const ssgpu_plan* plan, ssgpu_string_step* out, int32_t cap);
+int ssgpu_dict_close(ssgpu_ctx* ctx, const ssgpu_dict* base, const ssgpu_string_step* steps, int32_t n, ssgpu_dict** out, int32_t* remap);
+int ssgpu_dict_step_table(const ssgpu_dict* closed, int32_t k, int32_t* out_host);
+
 /* ---- device-resident Block ----------------------------------------------- */
 /* Layout (base/infrastructure/block.cc:20-36 allocates a buffer per column; so did this library until ABI 9): a block of 32 MiB or
  * more is ONE device allocation, column i's data starting i x (its 2 MiB-rounded size + 512 bytes) into it and the NULL masks

@@ -467,6 +467,15 @@ inline const Expression* ToLower(const Expression* a) { return internal::Op(420,
 inline const Expression* StringOffset(const Expression* haystack, const Expression* needle) { return internal::Op(476, haystack, needle); }
 inline const Expression* StringContains(const Expression* haystack, const Expression* needle) { return Less(ConstUint32(0), StringOffset(haystack, needle)); }
 inline const Expression* StringContainsCI(const Expression* haystack, const Expression* needle) { return StringContains(ToLower(haystack), ToLower(needle)); }
+// Functions whose result is a STRING (string_expressions.h:30-44,52-58): OPERATOR_LTRIM / RTRIM / TRIM / TOUPPER / SUBSTRING_SIGNALING.
+// The result is a code of the cursor's dictionary, which CreateCursor / Bind close under the tree's nodes on the device
+// (ssgpu.h "THE CLOSED DICTIONARY").  `pos` / `len` are integer constants (ConstInt64 ...) or Null; TrailingSubstring goes to the end.
+inline const Expression* Ltrim(const Expression* a) { return internal::Op(404, a); }
+inline const Expression* Rtrim(const Expression* a) { return internal::Op(408, a); }
+inline const Expression* Trim(const Expression* a) { return internal::Op(412, a); }
+inline const Expression* ToUpper(const Expression* a) { return internal::Op(416, a); }
+inline const Expression* Substring(const Expression* str, const Expression* pos, const Expression* len) { return internal::Op(427, str, pos, len); }
+inline const Expression* TrailingSubstring(const Expression* str, const Expression* pos) { return internal::Op(427, str, pos); }
 // owning list of expressions (expression/base/expression.h): the arguments of Case / In
 class ExpressionList {
  public:
@@ -651,6 +660,23 @@ struct Dictionary {
     for (rowcount_t i = 0; i < n; ++i) { ptr[i] = cells[i].data(); len[i] = static_cast<int32_t>(cells[i].size()); }
     codes->assign(static_cast<size_t>(std::max<rowcount_t>(n, 1)), 0);
     return ssgpu_dict_encode(d, ptr.data(), len.data(), reinterpret_cast<const uint8_t*>(is_null), static_cast<int64_t>(n), codes->data());
+  }
+  // String-producing nodes (Trim, ToUpper, Substring ...) make values of the SAME dictionary: closes it under the bound plan's steps on
+  // the device (ssgpu_plan_string_steps, ssgpu_dict_close).  *closed: the codes changed -- the caller encodes its ConstStrings again and
+  // binds anew.  A plan without such nodes, and a bind-only context (binding needs no device), leave the dictionary as it is.
+  int CloseFor(ssgpu_ctx* ctx, const ssgpu_plan* plan, bool* closed) {
+    *closed = false;
+    const int32_t n = ssgpu_plan_string_steps(plan, nullptr, 0);
+    if (n <= 0 || !d || !ssgpu_ctx_has_device(ctx)) return SSGPU_OK;
+    std::vector<ssgpu_string_step> steps(static_cast<size_t>(n));
+    ssgpu_plan_string_steps(plan, steps.data(), n);
+    std::vector<int32_t> remap(static_cast<size_t>(std::max<int32_t>(ssgpu_dict_size(d), 1)));
+    ssgpu_dict* out = nullptr;
+    const int rc = ssgpu_dict_close(ctx, d, steps.data(), n, &out, remap.data());
+    if (rc != SSGPU_OK) return rc;
+    ssgpu_dict_destroy(d);
+    d = out; *closed = true;
+    return SSGPU_OK;
   }
   StringPiece Decode(int32_t code) const {
     const char* b = nullptr; int32_t n = 0;
@@ -1022,8 +1048,23 @@ class BasicOperation : public Operation {
       d.aux_schema = aux_attrs.data(); d.n_aux_attrs = static_cast<int32_t>(aux_attrs.size());
     }
     ssgpu_plan* plan = nullptr;
-    const int rc = ssgpu_plan_create(ctx, &d, &plan);
+    int rc = ssgpu_plan_create(ctx, &d, &plan);
     if (rc != SSGPU_OK) return FailureOrOwned<Cursor>(new Exception(rc, ssgpu_last_error(ctx)));
+    // string-producing nodes: the dictionary is closed under the plan's steps, the ConstStrings are encoded again -- their codes
+    // are baked into the description -- and the plan is created anew over the closed dictionary
+    bool closed = false;
+    rc = c->dict_.CloseFor(ctx, plan, &closed);
+    if (rc == SSGPU_OK && closed) {
+      ssgpu_plan_destroy(plan); plan = nullptr;
+      for (size_t i = 0; rc == SSGPU_OK && i < b.string_consts.size(); ++i) {
+        StringPiece v(*b.string_consts[i].second); std::vector<int32_t> code;
+        rc = c->dict_.Encode(&v, nullptr, 1, &code);
+        b.exprs[static_cast<size_t>(b.string_consts[i].first)].i64 = code[0];
+      }
+      d.exprs = b.exprs.data();
+      if (rc == SSGPU_OK) rc = ssgpu_plan_create(ctx, &d, &plan);
+    }
+    if (rc != SSGPU_OK) { if (plan) ssgpu_plan_destroy(plan); return FailureOrOwned<Cursor>(new Exception(rc, ssgpu_last_error(ctx))); }
     if (c->dict_.d) ssgpu_plan_set_dict(plan, c->dict_.d);   // CONCAT prints STRING inputs through the cursor's dictionary
     // SetBufferAllocator(MemoryLimit): the plan's device buffers are charged to the allocator's remaining quota
     if (const BufferAllocator* a = EffectiveAllocator()) if (a->has_quota()) ssgpu_plan_set_memory_limit(plan, static_cast<int64_t>(a->Available()));
@@ -1258,6 +1299,21 @@ class BoundExpressionTree {
       attrs.push_back({input_schema_.attribute(i).name().c_str(), input_schema_.attribute(i).type(), input_schema_.attribute(i).nullability()});
     int rc = ssgpu_expr_bind(ctx, attrs.data(), static_cast<int32_t>(attrs.size()), exprs_.data(), static_cast<int32_t>(exprs_.size()),
                              expr_args_.data(), static_cast<int32_t>(expr_args_.size()), root_, static_cast<int64_t>(max_row_count_), &plan_);
+    if (rc != SSGPU_OK) return rc;
+    // as the cursor factory: close the dictionary under the tree's string-producing nodes, encode the ConstStrings again, bind anew
+    bool closed = false;
+    rc = dict_.CloseFor(ctx, plan_, &closed);
+    if (rc == SSGPU_OK && closed) {
+      ssgpu_plan_destroy(plan_); plan_ = nullptr;
+      for (size_t i = 0; rc == SSGPU_OK && i < string_consts_.size(); ++i) {
+        StringPiece v(string_consts_[i].second); std::vector<int32_t> code;
+        rc = dict_.Encode(&v, nullptr, 1, &code);
+        exprs_[static_cast<size_t>(string_consts_[i].first)].i64 = code[0];
+      }
+      if (rc == SSGPU_OK)
+        rc = ssgpu_expr_bind(ctx, attrs.data(), static_cast<int32_t>(attrs.size()), exprs_.data(), static_cast<int32_t>(exprs_.size()),
+                             expr_args_.data(), static_cast<int32_t>(expr_args_.size()), root_, static_cast<int64_t>(max_row_count_), &plan_);
+    }
     if (rc != SSGPU_OK) return rc;
     if (dict_.d) ssgpu_plan_set_dict(plan_, dict_.d);   // Length / StringOffset read the dictionary's values
     if (memory_limit_ >= 0) ssgpu_plan_set_memory_limit(plan_, memory_limit_);

@@ -104,6 +104,10 @@ class HostColumn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("is_null", C.c_void_p), ("offsets", C.c_void_p)]
 
 
+class StringStep(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("has_len", C.c_int32), ("pos", C.c_int64), ("len", C.c_int64)]
+
+
 class PartialSegment(C.Structure):
     _fields_ = [("device_ptr", C.c_void_p), ("count", C.c_int64), ("dtype", C.c_int32), ("reduce", C.c_int32)]
 
@@ -141,6 +145,9 @@ SYMBOLS = [
     ("ssgpu_dict_decode", C.c_int, [P, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]),
     ("ssgpu_dict_extend", C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int64, C.POINTER(P), C.POINTER(C.c_int32)]),
     ("ssgpu_dict_eval", C.c_int, [P, P, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("ssgpu_plan_string_steps", C.c_int32, [P, C.POINTER(StringStep), C.c_int32]),
+    ("ssgpu_dict_close", C.c_int, [P, P, C.POINTER(StringStep), C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]),
+    ("ssgpu_dict_step_table", C.c_int, [P, C.c_int32, C.POINTER(C.c_int32)]),
     ("ssgpu_codes_recode", C.c_int, [P, P, P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, P]),
     ("ssgpu_plan_set_memory_limit", C.c_int, [P, C.c_int64]),
     ("ssgpu_plan_set_dict", C.c_int, [P, P]),

@@ -125,6 +125,36 @@ class StringDictionary(object):
                                            out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
+    LTRIM, RTRIM, TRIM, TO_UPPER, TO_LOWER, SUBSTRING = 404, 408, 412, 416, 420, 427
+
+    def close(self, steps, context=None):
+        """ssgpu_dict_close: self closed under `steps` -- (fn,) / (fn, pos) / (fn, pos, len) tuples or ssgpu_string_step records, in
+        order -- on the device -> (dictionary, remap): every step's images joined in, remap[c] the new code of code c.  The result keeps
+        its steps (.steps) and one table per step (step_table)."""
+        ctx = context or Context.default()
+        recs = (L.StringStep * max(len(steps), 1))()
+        for i, st in enumerate(steps):
+            if isinstance(st, L.StringStep):
+                recs[i] = st
+                continue
+            st = tuple(st) if isinstance(st, (tuple, list)) else (st,)
+            recs[i] = L.StringStep(int(st[0]), 1 if len(st) > 2 else 0, int(st[1]) if len(st) > 1 else 0, int(st[2]) if len(st) > 2 else 0)
+        remap = np.zeros(max(len(self), 1), np.int32)
+        h = C.c_void_p()
+        ctx.check(self.lib.ssgpu_dict_close(ctx.handle, self.handle, recs, len(steps), C.byref(h), remap.ctypes.data_as(C.POINTER(C.c_int32))))
+        d = StringDictionary.__new__(StringDictionary)
+        d.lib, d.handle = self.lib, h
+        d.steps = [(r.fn, r.has_len, r.pos, r.len) for r in recs[:len(steps)]]
+        return d, remap[:len(self)]
+
+    def step_table(self, k):
+        """ssgpu_dict_step_table: T_k of a closed dictionary -> int32[len(self)], T_k[code(v)] = code(f_k(v)) where v was there before step k, else 0."""
+        out = np.zeros(max(len(self), 1), np.int32)
+        rc = self.lib.ssgpu_dict_step_table(self.handle, int(k), out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != L.OK:
+            raise SupersonicException(rc, "the dictionary has no step %d (StringDictionary.close)" % int(k))
+        return out[:len(self)]
+
     def encode(self, data, nulls):
         n = len(data)
         out = np.zeros(n, np.int32)
@@ -710,6 +740,14 @@ def ToLower(a): return _op(420, a)                 # only as both arguments of a
 def StringOffset(haystack, needle): return _op(476, haystack, needle)
 def StringContains(haystack, needle): return Less(ConstUint32(0), StringOffset(haystack, needle))      # string_bound_expressions.cc:179-189
 def StringContainsCI(haystack, needle): return StringContains(ToLower(haystack), ToLower(needle))      # :193-205
+# functions whose result is a STRING (string_expressions.h:30-44,52-58): codes of the plan's dictionary CLOSED under them (StringDictionary.close);
+# `pos` / `length` are integer constants (ConstInt64(..) ...) or Null
+def Ltrim(a): return _op(404, a)
+def Rtrim(a): return _op(408, a)
+def Trim(a): return _op(412, a)
+def ToUpper(a): return _op(416, a)
+def Substring(s, pos, length): return _op(427, s, pos, length)
+def TrailingSubstring(s, pos): return _op(427, s, pos)
 
 
 class ExpressionList(object):
@@ -1130,6 +1168,16 @@ def _dict_blocks(operation):
     return found
 
 
+def _string_steps(lib, plan_handle):
+    """ssgpu_plan_string_steps -> the plan's step list as ssgpu_string_step records ([] for a plan without string-producing nodes)."""
+    n = lib.ssgpu_plan_string_steps(plan_handle, None, 0)
+    if n <= 0:
+        return []
+    recs = (L.StringStep * n)()
+    lib.ssgpu_plan_string_steps(plan_handle, recs, n)
+    return [L.StringStep(r.fn, r.has_len, r.pos, r.len) for r in recs]
+
+
 def _find_allocator(operation):
     """The allocator set on the nearest operation from the root (SetBufferAllocator cascades downwards)."""
     o = operation
@@ -1227,6 +1275,33 @@ class Plan(object):
                     self.strings, self._base_remap = ext, (blocks[0], remap)
         else:
             self.strings = StringDictionary(strings)
+        h = self._create(operation, b)
+        # string-producing nodes (Trim, ToUpper, Substring ...): their results must be codes of the plan's dictionary too, so the
+        # dictionary is closed under the plan's steps on the device and -- STRING constants are baked into the description as codes --
+        # the description is emitted and the plan created again over the closed one.  A plan without such nodes stops here, and a
+        # bind-only context keeps the first plan: binding, describe() and the result schema need no device.
+        steps = _string_steps(self.lib, h)
+        if steps and self.lib.ssgpu_ctx_has_device(context.handle):
+            try:
+                closed, cremap = self.strings.close(steps, context)
+                if self._base_remap is not None:       # a device block is still recoded once: extend's remap, then the closure's
+                    self._base_remap = (self._base_remap[0], cremap[self._base_remap[1]])
+                elif blocks:
+                    self._base_remap = (blocks[0], cremap)
+                self.strings = closed
+                h2 = self._create(operation, _Builder())
+            finally:
+                self.lib.ssgpu_plan_destroy(h)
+            h = h2
+        self._adopt(h)
+        self.lib.ssgpu_plan_set_dict(h, self.strings.handle)      # CONCAT prints STRING inputs through the plan's dictionary
+        alloc = _find_allocator(operation)
+        if alloc is not None:
+            self.set_buffer_allocator(alloc)
+
+    def _create(self, operation, b):
+        """Emits the operation tree against self.strings and creates the plan -> its handle."""
+        context = self.ctx
         b.strings = self.strings
         operation._emit(b)
         if b.scan is None:
@@ -1257,11 +1332,7 @@ class Plan(object):
         h = C.c_void_p()
         rc = self.lib.ssgpu_plan_create(context.handle, C.byref(d), C.byref(h))
         context.check(rc)
-        self._adopt(h)
-        self.lib.ssgpu_plan_set_dict(h, self.strings.handle)      # CONCAT prints STRING inputs through the plan's dictionary
-        alloc = _find_allocator(operation)
-        if alloc is not None:
-            self.set_buffer_allocator(alloc)
+        return h
 
     def _adopt(self, h):
         self.handle = h
@@ -1714,8 +1785,24 @@ class BoundExpressionTree(Plan):
         because the codes of its constants depend on the View's values (one dictionary per evaluated View)."""
         if self.handle:
             self._release()
+        self.strings = StringDictionary(strings)
+        h = self._bind_handle()
+        steps = _string_steps(self.lib, h)           # as Plan.__init__: close the dictionary under the tree's producers, bind again
+        if steps and self.lib.ssgpu_ctx_has_device(self.ctx.handle):
+            try:
+                self.strings, _remap = self.strings.close(steps, self.ctx)
+                h2 = self._bind_handle()
+            finally:
+                self.lib.ssgpu_plan_destroy(h)
+            h = h2
+        self._adopt(h)
+        self.lib.ssgpu_plan_set_dict(h, self.strings.handle)      # LENGTH / STRING_OFFSET read the dictionary's values
+        if self.allocator is not None:
+            self.set_buffer_allocator(self.allocator)
+
+    def _bind_handle(self):
         b = _Builder()
-        b.strings = self.strings = StringDictionary(strings)
+        b.strings = self.strings
         root = b.expr(self.expression)
         schema = self.input_schema
         attrs = _array(L.Attr, [L.Attr(b.s(schema.attribute(i).name()), schema.attribute(i).type(), schema.attribute(i).nullability())
@@ -1724,10 +1811,7 @@ class BoundExpressionTree(Plan):
         h = C.c_void_p()
         self.ctx.check(self.lib.ssgpu_expr_bind(self.ctx.handle, attrs, schema.attribute_count(), self._keep[2], len(b.exprs),
                                                 self._keep[3], len(b.expr_args), root, self.max_row_count, C.byref(h)))
-        self._adopt(h)
-        self.lib.ssgpu_plan_set_dict(h, self.strings.handle)      # LENGTH / STRING_OFFSET read the dictionary's values
-        if self.allocator is not None:
-            self.set_buffer_allocator(self.allocator)
+        return h
 
     def row_capacity(self):
         return self.lib.ssgpu_expr_row_capacity(self.handle)

@@ -30,7 +30,7 @@ enum {
   OP_ASIN = 812, OP_ACOS = 816, OP_ATAN = 820, OP_ATAN2 = 824, OP_SINH = 828, OP_COSH = 832, OP_TANH = 836, OP_ASINH = 840,
   OP_ACOSH = 844, OP_ATANH = 848,
   OP_SQRT_QUIET = 333, OP_SQRT_NULLING = 334, OP_SQRT_SIGNALING = 335, OP_CEIL = 342, OP_FLOOR = 346, OP_ABS = 360,
-  OP_LENGTH = 400, OP_TOLOWER = 420, OP_STRING_OFFSET = 476,
+  OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_TOLOWER = 420, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476,
   OP_CASE = 200, OP_IF = 204, OP_IN = 208, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265
 };
 
@@ -726,6 +726,46 @@ static Status bind_operator(const ssgpu_expr& x, std::vector<BExprP> args, int d
         return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("LENGTH needs a STRING argument, got ") + dtype_name(args[0]->dtype) + " in " + args[0]->name);
       *out = make_op(op, SSGPU_UINT32, args[0]->nullable, "LENGTH(" + args[0]->name + ")", {args[0]}, depth);
       return Status::OK();
+    // ---- functions whose result is a STRING: a code of the plan's CLOSED dictionary, gathered from a table the dictionary brings
+    // along (ssgpu.h "THE CLOSED DICTIONARY"; lower.cpp).  Names and refusals: string_expressions_test.cc:37-87.
+    case OP_LTRIM: case OP_RTRIM: case OP_TRIM: case OP_TOUPPER: {
+      const char* nm = op == OP_LTRIM ? "LTRIM" : op == OP_RTRIM ? "RTRIM" : op == OP_TRIM ? "TRIM" : "TO_UPPER";
+      SS_RETURN_IF_ERROR(need(1));
+      if (args[0]->dtype != SSGPU_STRING)
+        return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string(nm) + " needs a STRING argument, got " + dtype_name(args[0]->dtype) + " in " + args[0]->name);
+      *out = make_op(op, SSGPU_STRING, args[0]->nullable, std::string(nm) + "(" + args[0]->name + ")", {args[0]}, depth);
+      return Status::OK();
+    }
+    case OP_SUBSTRING: {
+      if (args.size() != 2 && args.size() != 3)
+        return Status::Error(SSGPU_ERROR_ATTRIBUTE_COUNT_MISMATCH, "SUBSTRING expects 2 or 3 single-attribute arguments");
+      if (args[0]->dtype != SSGPU_STRING)
+        return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("SUBSTRING needs a STRING first argument, got ") + dtype_name(args[0]->dtype) + " in " + args[0]->name);
+      // the position and the length are INT64 in the reference's signature; any integer type is promoted (BindingWithCast), nothing else is
+      std::vector<BExprP> num;
+      for (size_t i = 1; i < args.size(); ++i) {
+        if (!dtype_is_integer(args[i]->dtype))
+          return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("SUBSTRING needs an integer ") + (i == 1 ? "position" : "length") + ", got " +
+                                                                        dtype_name(args[i]->dtype) + " in " + args[i]->name);
+        BExprP c;
+        SS_RETURN_IF_ERROR(make_cast(args[i], SSGPU_INT64, true, &c));
+        num.push_back(c);
+      }
+      std::string name = "SUBSTRING(" + args[0]->name;
+      for (const BExprP& c : num) name += ", " + c->name;
+      name += ")";
+      for (size_t i = 0; i < num.size(); ++i)
+        if (!is_constant(num[i]))
+          return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, std::string("SUBSTRING: the ") + (i == 0 ? "position" : "length") + " must be an integer constant or NULL (one table per "
+                                                            "(position, length) is built over the dictionary); one that varies per row (" + num[i]->name + ") is outside the device hot path");
+      bool nullable = args[0]->nullable, null_arg = false;
+      for (const BExprP& c : num) { nullable = nullable || c->nullable; null_arg = null_arg || c->kind == BExpr::NULLCONST; }
+      BExprP e = make_op(op, SSGPU_STRING, nullable, name, {args[0]}, depth);
+      e->str_null = null_arg; e->str_has_len = num.size() == 2;
+      if (!null_arg) { e->str_pos = bits_to_i64(SSGPU_INT64, num[0]->bits); if (e->str_has_len) e->str_len = bits_to_i64(SSGPU_INT64, num[1]->bits); }
+      *out = e;
+      return Status::OK();
+    }
     case OP_TOLOWER:
       // a marker, never a value: bind_expression lets it through only as an argument of STRING_OFFSET, which takes it apart
       SS_RETURN_IF_ERROR(need(1));

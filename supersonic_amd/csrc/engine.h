@@ -23,6 +23,11 @@ extern "C" int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offset
 // ... and the other way: a dictionary's values packed for the device (`offsets[n + 1]`, `heap` of ssgpu_dict_heap_bytes bytes)
 extern "C" uint64_t ssgpu_dict_heap_bytes(const ssgpu_dict* d);
 extern "C" void ssgpu_dict_pack(const ssgpu_dict* d, uint64_t* offsets, char* heap);
+// a closed dictionary's step list and tables (ssgpu_dict_close writes them, ensure_dict_tables reads them)
+extern "C" void ssgpu_dict_set_steps(ssgpu_dict* d, const ssgpu_string_step* steps, int32_t n, const int32_t* tables);
+extern "C" int32_t ssgpu_dict_step_count(const ssgpu_dict* d);
+extern "C" const ssgpu_string_step* ssgpu_dict_step(const ssgpu_dict* d, int32_t k);
+extern "C" const int32_t* ssgpu_dict_step_table_data(const ssgpu_dict* d, int32_t k);
 
 namespace ssgpu {
 
@@ -63,6 +68,10 @@ struct BExpr {
   int join_id = -1;    // JOINCOL / JOINMATCH / JOINSTART / JOINCNT: index into the stage's joins
   uint64_t bits = 0;   // CONST: raw value bits in the column's device width
   int filter_depth = 0;  // number of Filter operations below this expression
+  // string-producing OP (LTRIM 404 ... SUBSTRING 427; args = the STRING argument alone): SUBSTRING's constant position and length
+  // (str_has_len: the 3-argument form); str_null: a NULL position / length -- the result is NULL everywhere and needs no table
+  int64_t str_pos = 0, str_len = 0;
+  bool str_has_len = false, str_null = false;
   std::vector<BExprP> args;
 };
 
@@ -105,9 +114,15 @@ struct JoinSpec {
 };
 // slot i of VmParams.join_cols: a column (or NULL mask) of a join's rhs table, or -- join_id == JOIN_GATHER_DICT_TABLE -- a table
 // over the plan's STRING dictionary, indexed by a code: table[c] = fn(value c) (string_fn_kernels.hip), fn = 400 LENGTH,
-// 476 STRING_OFFSET of the value whose code is `needle_code`, compared through ascii_tolower when `fold`
-struct JoinGather { int join_id; int rhs_col; bool is_null_mask; int fn = 0; int32_t needle_code = 0; bool fold = false; };
+// 476 STRING_OFFSET of the value whose code is `needle_code`, compared through ascii_tolower when `fold`; or the table of a
+// string-producing function (is_string_producer(fn): 404 / 408 / 412 / 416 / 427 with SUBSTRING's pos / len / has_len), table[c] = the
+// code of fn(value c) in the plan's CLOSED dictionary, which holds it (ssgpu_dict_close; runtime.cpp only uploads it)
+struct JoinGather {
+  int join_id; int rhs_col; bool is_null_mask; int fn = 0; int32_t needle_code = 0; bool fold = false;
+  int64_t pos = 0, len = 0; bool has_len = false;
+};
 enum { JOIN_GATHER_DICT_TABLE = -2 };
+inline bool is_string_producer(int fn) { return fn == 404 || fn == 408 || fn == 412 || fn == 416 || fn == 427; }
 enum { JOIN_GATHER_RUN_START = -1, JOIN_GATHER_RUN_COUNT = -2 };   // rhs_col of a multi join's per-key run arrays
 
 // Lowered instruction over virtual registers.  A register is an LDS array of
@@ -130,7 +145,8 @@ struct Program {
   std::vector<LReg> regs;
   std::vector<StagedInput> staged;
   std::vector<JoinGather> gathers;   // rhs columns (and NULL masks) read by GATHER_* instructions
-  bool uses_math = false;            // has MATH1_F64 / MATH2_F64: runs in the MATH kernel variant
+  std::vector<ssgpu_string_step> string_steps;   // the program's string-producing nodes in evaluation order (ssgpu_plan_string_steps)
+  bool uses_math = false;           // has MATH1_F64 / MATH2_F64: runs in the MATH kernel variant
   uint32_t bytes_per_row = 0;   // LDS bytes per tile row (peak of live registers)
   uint32_t in_bytes_per_row = 0;  // of which: the staged input registers
   int n_slots = 0;

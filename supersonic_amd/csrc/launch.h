@@ -339,6 +339,16 @@ hipError_t ssgpu_launch_str_recode(const int32_t* src, const uint8_t* nulls, con
 #define STRFN_HEAP_PAD 32
 hipError_t ssgpu_launch_str_fn(const uint8_t* heap, const uint64_t* offs, uint64_t n, int fn, const uint8_t* needle, uint32_t needle_len,
                                int fold, uint32_t* table, hipStream_t s);
+// string-producing functions of the dictionary's values (string_map_kernels.hip), one closing step of ssgpu_dict_close: the length
+// pass fills lens[0, n) with the values' own lengths, lens[n, 2n) with their images' and src[i] with the image's first byte in `heap`
+// (fn: 404 LTRIM, 408 RTRIM, 412 TRIM, 416 TO_UPPER, 420 TO_LOWER, 427 SUBSTRING(pos, len) -- to the end without has_len); the write
+// pass copies image i to out[dst_offs[i], dst_offs[i + 1]), dir 1 folding a-z to A-Z, 2 A-Z to a-z, 0 as it is.  Same heap contract
+// as ssgpu_launch_str_fn.  compose: see the kernel.
+hipError_t ssgpu_launch_str_map_len(const uint8_t* heap, const uint64_t* offs, uint64_t n, int fn, int has_len, int64_t pos, int64_t len,
+                                    uint64_t* lens, uint64_t* src, hipStream_t s);
+hipError_t ssgpu_launch_str_map_write(const uint8_t* heap, const uint64_t* src, const uint64_t* dst_offs, uint64_t n, int dir, uint8_t* out, hipStream_t s);
+hipError_t ssgpu_launch_str_map_compose(const int32_t* codes, uint64_t n, const int32_t* later, uint64_t n_later, uint64_t n_final, int32_t* to_final,
+                                        int32_t* table, hipStream_t s);
 hipError_t ssgpu_launch_sort_unkey(void* out, const uint64_t* keys, uint32_t width, int kind, int descending, uint64_t n, hipStream_t s);
 hipError_t ssgpu_launch_sort_gather(void* out, uint8_t* out_nulls, const void* col, const uint8_t* nulls, uint32_t width,
                                     const uint32_t* idx, uint64_t n, hipStream_t s);

@@ -34,7 +34,7 @@ enum {
   OP_AND_NOT = 48, OP_NOT = 52, OP_XOR = 56, OP_BITWISE_AND = 60, OP_BITWISE_OR = 64,
   OP_BITWISE_NOT = 68, OP_BITWISE_XOR = 72, OP_SHIFT_LEFT = 76, OP_SHIFT_RIGHT = 80,
   OP_BITWISE_ANDNOT = 84, OP_EQUAL = 100, OP_NOT_EQUAL = 104, OP_LESS = 116, OP_LESS_OR_EQUAL = 120,
-  OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265, OP_LENGTH = 400, OP_STRING_OFFSET = 476
+  OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265, OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476
 };
 
 // machine type classes
@@ -149,6 +149,16 @@ class Emitter {
     P->gathers.push_back(g);
     return (int)P->gathers.size() - 1;
   }
+  // ... and the table of a string-producing function, keyed by (function, position, length): the plan's closed dictionary brings it
+  int producer_slot(int fn, int64_t pos, int64_t len, bool has_len) {
+    for (size_t i = 0; i < P->gathers.size(); ++i) {
+      const JoinGather& t = P->gathers[i];
+      if (t.join_id == JOIN_GATHER_DICT_TABLE && t.fn == fn && t.pos == pos && t.len == len && t.has_len == has_len) return (int)i;
+    }
+    JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.fn = fn; g.pos = pos; g.len = len; g.has_len = has_len;
+    P->gathers.push_back(g);
+    return (int)P->gathers.size() - 1;
+  }
 
   // join_index: the stage's filter chain and whether later filters may be evaluated ahead of a probe (emit_filters sets both)
   const std::vector<BExprP>* filters_ = nullptr;
@@ -223,6 +233,7 @@ std::string Emitter::key_of(const BExprP& e) {
     default:
       s << (e->kind == BExpr::CAST ? "K" : "O") << e->op << ":" << e->dtype << ":" << e->filter_depth;
       if (e->kind == BExpr::OP && e->op == OP_STRING_OFFSET) s << (e->bits ? "ci" : "cs");   // BExpr::bits: compared through ascii_tolower
+      if (e->kind == BExpr::OP && e->op == OP_SUBSTRING) s << "@" << e->str_pos << ":" << e->str_len << ":" << e->str_has_len << e->str_null;
       s << "(";
       for (auto& a : e->args) s << key_of(a) << ",";
       s << ")";
@@ -571,6 +582,20 @@ Status Emitter::value(const BExprP& e, Val* out) {
           if (offset && e->args[1]->kind == BExpr::NULLCONST) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // NULL needle
           const int code = materialize(a[0]);
           const int slot = table_slot(offset ? OP_STRING_OFFSET : OP_LENGTH, offset ? (int32_t)(uint32_t)e->args[1]->bits : 0, offset && e->bits != 0);
+          v.reg = new_reg(4);
+          LInstr& i = emit(VM_GATHER_32); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot;
+          v.null = a[0].null;
+        } break;
+        case OP_LTRIM: case OP_RTRIM: case OP_TRIM: case OP_TOUPPER: case OP_SUBSTRING: {
+          // f(s) = T[code(s)] again, with T[c] = the code of f(value c): the plan's dictionary is closed under the plan's producer
+          // nodes (ssgpu_dict_close), so the result is a code of the same dictionary and everything above works on it as on a column.
+          // Every entry of T is a valid code, so a nested producer gathers with whatever this one read.  The node joins the
+          // program's step list here -- after its argument: post-order.
+          if (e->str_null) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // NULL position / length
+          const int code = materialize(a[0]);
+          const int slot = producer_slot(e->op, e->str_pos, e->str_len, e->str_has_len);
+          ssgpu_string_step step; step.fn = e->op; step.has_len = e->str_has_len ? 1 : 0; step.pos = e->str_pos; step.len = e->str_len;
+          P->string_steps.push_back(step);
           v.reg = new_reg(4);
           LInstr& i = emit(VM_GATHER_32); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot;
           v.null = a[0].null;

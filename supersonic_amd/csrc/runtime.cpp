@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
+#include <chrono>
 #include <map>
 #include <tuple>
 #include <set>
@@ -397,11 +398,15 @@ struct ssgpu_plan {
   // once, one table of 4-byte entries per (function, needle code, fold).  Dictionaries are immutable, so the tables are built lazily
   // before the first run that needs them and again when the plan is handed another dictionary (dict_gen: the stamp of the
   // ssgpu_plan_set_dict call, so that a new dictionary at a freed one's address is not mistaken for it); freed with the plan.
+  // The table of a string-producing node (LTRIM ... SUBSTRING) is not computed here: the plan's CLOSED dictionary brings it along
+  // (ssgpu_dict_close) and ensure_dict_tables uploads it, after checking that the dictionary was closed under the plan's steps.
   uint64_t dict_gen = 0;
   struct DictTables {
     bool built = false; uint64_t built_gen = 0; const ssgpu_dict* built_for = nullptr;
     DictDevice dev; DevBuf needle;
-    std::map<std::tuple<int, int32_t, bool>, DevBuf> tables;
+    typedef std::tuple<int, int32_t, bool, int64_t, int64_t, bool> Key;   // function, needle code, fold; a producer's position, length, has_len
+    static Key key(const JoinGather& g) { return Key(g.fn, g.needle_code, g.fold, g.pos, g.len, g.has_len); }
+    std::map<Key, DevBuf> tables;
   } dict_tables;
   std::vector<ssgpu_column> last_cols; int64_t last_base = 0; bool last_partial = false;   // the last run's input (a deferred overflow repeats it)
   // ssgpu_plan_run_host: two alternating sets of device columns the host rows are staged through, and the chunks' partial states
@@ -654,30 +659,36 @@ static bool read_slab(FILE* f, char* dst, size_t bytes) {
 // words: the byte lengths, scanned here into offsets into `heap`; `dnull` one NULL byte per domain row.  Runs on the copy
 // stream, writes the codes into the block's STRING columns and gives the block its dictionary.
 static const int64_t kMaxStringDomain = int64_t(1) << 30;   // the table's slot numbers stay 32-bit
-static int encode_string_domain(ssgpu_ctx* c, ssgpu_block* b, const std::vector<int>& scols, DevBuf& heap, DevBuf& lens, DevBuf& dnull) {
-  hipStream_t s = c->copy_stream;
-  const uint64_t rows = (uint64_t)b->rows, n = rows * scols.size();
-  std::vector<uint64_t> off_h(1, 0);
-  std::vector<char> heap_h;
+// The device part, for any domain of n rows (`lens`: n + 1 words, `dnull`: n bytes): the distinct values sorted in StringPiece order
+// -- on the device as out_off[D + 1] / out_heap (`heap_pad` bytes of slack behind the values, for readers of aligned words) and copied
+// back once into off_h / heap_h -- and, for every target, codes[first + r] of its `rows` domain rows written to dst (0 for a NULL row).
+// `scanned`: lens already holds the offsets (the caller needed the total to size the heap).  Returns with the stream idle.
+struct DomainCodes { int32_t* dst; uint64_t first, rows; };
+static int encode_domain(ssgpu_ctx* c, hipStream_t s, const uint8_t* bytes, uint64_t* lens, bool scanned, const uint8_t* dnull, uint64_t n,
+                         const std::vector<DomainCodes>& targets, uint64_t heap_pad, std::vector<uint64_t>* off_h_out, std::vector<char>* heap_h_out,
+                         uint32_t* D_out, DevBuf& out_off, DevBuf& out_heap) {
+  std::vector<uint64_t>& off_h = *off_h_out;
+  std::vector<char>& heap_h = *heap_h_out;
+  off_h.assign(1, 0);
+  heap_h.clear();
   uint32_t D = 0;
   if (n) {
     uint64_t cap = 64, np2 = 1;
     while (cap < 2 * n) cap <<= 1;
     while (np2 < n) np2 <<= 1;
-    DevBuf partials, hashes, table, row_slot, flags, d_slot, d_off, d_len, d_key, d_idx, slot_rank, out_off, out_heap;
+    DevBuf partials, hashes, table, row_slot, flags, d_slot, d_off, d_len, d_key, d_idx, slot_rank;
     const bool alloc_ok =
         partials.ensure(ssgpu_str_scan_partials(n) * 8) == hipSuccess && hashes.ensure(n * 8) == hipSuccess && table.ensure(cap * 8) == hipSuccess &&
         row_slot.ensure(n * 4) == hipSuccess && flags.ensure(8) == hipSuccess && d_slot.ensure(n * 4) == hipSuccess && d_off.ensure(n * 8) == hipSuccess &&
         d_len.ensure(n * 8) == hipSuccess && d_key.ensure(np2 * 8) == hipSuccess && d_idx.ensure(np2 * 4) == hipSuccess &&
         slot_rank.ensure(cap * 4) == hipSuccess && out_off.ensure((n + 1) * 8) == hipSuccess;
     if (!alloc_ok) { c->err = "Memory exceeded: the STRING dictionary's device tables"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
-    const uint8_t* bytes = heap.as<uint8_t>();
-    const uint64_t* offs = lens.as<uint64_t>();
-    HIP_TRY(c, ssgpu_launch_str_scan(lens.as<uint64_t>(), n, partials.as<uint64_t>(), s));
-    HIP_TRY(c, ssgpu_launch_str_hash(bytes, offs, dnull.as<uint8_t>(), n, hashes.as<uint64_t>(), s));
+    const uint64_t* offs = lens;
+    if (!scanned) HIP_TRY(c, ssgpu_launch_str_scan(lens, n, partials.as<uint64_t>(), s));
+    HIP_TRY(c, ssgpu_launch_str_hash(bytes, offs, dnull, n, hashes.as<uint64_t>(), s));
     HIP_TRY(c, hipMemsetAsync(table.p, 0, cap * 8, s));
     HIP_TRY(c, hipMemsetAsync(flags.p, 0, 8, s));
-    HIP_TRY(c, ssgpu_launch_str_insert(bytes, offs, dnull.as<uint8_t>(), hashes.as<uint64_t>(), n, table.as<uint64_t>(), cap, row_slot.as<uint32_t>(),
+    HIP_TRY(c, ssgpu_launch_str_insert(bytes, offs, dnull, hashes.as<uint64_t>(), n, table.as<uint64_t>(), cap, row_slot.as<uint32_t>(),
                                        flags.as<uint32_t>() + 1, s));
     HIP_TRY(c, ssgpu_launch_str_compact(table.as<uint64_t>(), cap, bytes, offs, flags.as<uint32_t>(), d_slot.as<uint32_t>(), d_off.as<uint64_t>(),
                                         d_len.as<uint64_t>(), d_key.as<uint64_t>(), d_idx.as<uint32_t>(), s));
@@ -691,18 +702,31 @@ static int encode_string_domain(ssgpu_ctx* c, ssgpu_block* b, const std::vector<
     HIP_TRY(c, ssgpu_launch_str_sort(d_key.as<uint64_t>(), d_idx.as<uint32_t>(), D, D ? p2 : 0, bytes, d_off.as<uint64_t>(), d_len.as<uint64_t>(), s));
     HIP_TRY(c, ssgpu_launch_str_rank(d_idx.as<uint32_t>(), d_slot.as<uint32_t>(), d_len.as<uint64_t>(), D, slot_rank.as<int32_t>(), out_off.as<uint64_t>(), s));
     HIP_TRY(c, ssgpu_launch_str_scan(out_off.as<uint64_t>(), D, partials.as<uint64_t>(), s));
-    for (size_t k = 0; k < scols.size(); ++k)
-      HIP_TRY(c, ssgpu_launch_str_codes(row_slot.as<uint32_t>() + k * rows, dnull.as<uint8_t>() + k * rows, slot_rank.as<int32_t>(), rows,
-                                        b->data[scols[k]].as<int32_t>(), s));
+    for (const DomainCodes& t : targets)
+      HIP_TRY(c, ssgpu_launch_str_codes(row_slot.as<uint32_t>() + t.first, dnull + t.first, slot_rank.as<int32_t>(), t.rows, t.dst, s));
     off_h.resize((size_t)D + 1);
     HIP_TRY(c, hipMemcpyAsync(off_h.data(), out_off.p, ((size_t)D + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (out_heap.ensure(std::max<uint64_t>(off_h[D], 1)) != hipSuccess) { c->err = "Memory exceeded: the STRING dictionary's values"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
+    if (out_heap.ensure(std::max<uint64_t>(off_h[D], 1) + heap_pad) != hipSuccess) { c->err = "Memory exceeded: the STRING dictionary's values"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
+    if (heap_pad) HIP_TRY(c, hipMemsetAsync(static_cast<char*>(out_heap.p) + off_h[D], 0, heap_pad, s));
     HIP_TRY(c, ssgpu_launch_str_gather(bytes, d_off.as<uint64_t>(), d_idx.as<uint32_t>(), out_off.as<uint64_t>(), D, out_heap.as<uint8_t>(), s));
     heap_h.resize((size_t)off_h[D]);
     if (off_h[D]) HIP_TRY(c, hipMemcpyAsync(heap_h.data(), out_heap.p, (size_t)off_h[D], hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
   }
+  *D_out = D;
+  return SSGPU_OK;
+}
+static int encode_string_domain(ssgpu_ctx* c, ssgpu_block* b, const std::vector<int>& scols, DevBuf& heap, DevBuf& lens, DevBuf& dnull) {
+  const uint64_t rows = (uint64_t)b->rows, n = rows * scols.size();
+  std::vector<uint64_t> off_h;
+  std::vector<char> heap_h;
+  uint32_t D = 0;
+  std::vector<DomainCodes> targets;
+  for (size_t k = 0; k < scols.size(); ++k) targets.push_back({b->data[scols[k]].as<int32_t>(), k * rows, rows});
+  DevBuf out_off, out_heap;
+  const int erc = encode_domain(c, c->copy_stream, heap.as<uint8_t>(), lens.as<uint64_t>(), false, dnull.as<uint8_t>(), n, targets, 0, &off_h, &heap_h, &D, out_off, out_heap);
+  if (erc != SSGPU_OK) return erc;
   ssgpu_dict* d = nullptr;
   const int rc = ssgpu_dict_create_sorted(heap_h.data(), off_h.data(), (int64_t)D, &d);
   if (rc != SSGPU_OK) { c->err = "STRING dictionary: too many distinct values"; return rc; }
@@ -1090,12 +1114,18 @@ int ssgpu_plan_attr(const ssgpu_plan* p, int32_t i, ssgpu_attr* out) {
 const char* ssgpu_plan_describe(ssgpu_plan* p) {
   if (!p) return "";
   // one line per table over the STRING dictionary: function, needle (its length once the dictionary is known), case folding
-  std::set<std::tuple<int, int32_t, bool>> seen;
+  std::set<ssgpu_plan::DictTables::Key> seen;
   std::string lines;
   for (auto& st : p->stages)
     for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
       for (auto& g : pr->gathers) {
-        if (g.join_id != JOIN_GATHER_DICT_TABLE || !seen.insert(std::make_tuple(g.fn, g.needle_code, g.fold)).second) continue;
+        if (g.join_id != JOIN_GATHER_DICT_TABLE || !seen.insert(ssgpu_plan::DictTables::key(g)).second) continue;
+        if (is_string_producer(g.fn)) {
+          lines += std::string("dictionary table: ") + (g.fn == 404 ? "LTRIM" : g.fn == 408 ? "RTRIM" : g.fn == 412 ? "TRIM" : g.fn == 416 ? "TO_UPPER" : "SUBSTRING");
+          if (g.fn == 427) lines += " position " + std::to_string(g.pos) + (g.has_len ? " length " + std::to_string(g.len) : std::string(" to the end"));
+          lines += " (codes of the closed dictionary)\n";
+          continue;
+        }
         if (g.fn != 476) { lines += "dictionary table: LENGTH\n"; continue; }
         const char* bytes = nullptr; int32_t len = 0;
         lines += "dictionary table: STRING_OFFSET needle code " + std::to_string(g.needle_code) +
@@ -1316,6 +1346,15 @@ int dict_table_build(ssgpu_ctx* c, const DictDevice& D, int fn, const char* need
                                  fold ? 1 : 0, table->as<uint32_t>(), c->stream));
   return SSGPU_OK;
 }
+// the plan's step list (ssgpu_plan_string_steps): the string-producing nodes of every program of every stage, in the order they are evaluated
+static void plan_string_steps(const ssgpu_plan* p, std::vector<ssgpu_string_step>* out) {
+  for (auto& st : p->stages)
+    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
+      out->insert(out->end(), pr->string_steps.begin(), pr->string_steps.end());
+}
+static bool same_step(const ssgpu_string_step& a, const ssgpu_string_step& b) {
+  return a.fn == b.fn && (a.fn != 427 || (a.pos == b.pos && (a.has_len != 0) == (b.has_len != 0) && (!a.has_len || a.len == b.len)));
+}
 static bool plan_has_dict_tables(const ssgpu_plan* p) {
   for (auto& st : p->stages)
     for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
@@ -1326,24 +1365,64 @@ static bool plan_has_dict_tables(const ssgpu_plan* p) {
 int ensure_dict_tables(ssgpu_plan* p) {
   if (!plan_has_dict_tables(p)) return SSGPU_OK;
   ssgpu_ctx* c = p->ctx;
-  if (!p->dict) { c->err = "LENGTH / STRING_OFFSET of a STRING value need the plan's dictionary (ssgpu_plan_set_dict)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  if (!p->dict) {
+    std::vector<ssgpu_string_step> producers;
+    plan_string_steps(p, &producers);
+    c->err = producers.empty() ? "LENGTH / STRING_OFFSET of a STRING value need the plan's dictionary (ssgpu_plan_set_dict)"
+                               : "LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING need the plan's dictionary, closed under the plan's steps (ssgpu_plan_string_steps, "
+                                 "ssgpu_dict_close, ssgpu_plan_set_dict)";
+    return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  }
   ssgpu_plan::DictTables& T = p->dict_tables;
   if (T.built && T.built_for == p->dict && T.built_gen == p->dict_gen) return SSGPU_OK;
   T.built = false;
+  // String-producing nodes gather from the tables the CLOSED dictionary brings along (ssgpu_dict_close): the run computes nothing, but it
+  // reads no table that is not its own -- the plan's step list must be a subsequence of the list the dictionary was closed under (a later
+  // step's domain contains every earlier one's; the derived plans of chunked execution, the NaN-exact repeat and the skip form hold subsets)
+  std::vector<ssgpu_string_step> steps;
+  plan_string_steps(p, &steps);
+  const int32_t dict_steps = ssgpu_dict_step_count(p->dict);
+  { int32_t k = 0;
+    for (const ssgpu_string_step& s : steps) {
+      while (k < dict_steps && !same_step(*ssgpu_dict_step(p->dict, k), s)) ++k;
+      if (k == dict_steps) {
+        c->err = std::string("LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING make STRING values: the plan's dictionary must be closed under the plan's ") +
+                 std::to_string(steps.size()) + " step(s) (ssgpu_plan_string_steps, ssgpu_dict_close, ssgpu_plan_set_dict); this one " +
+                 (dict_steps ? "was closed under another list of " + std::to_string(dict_steps) + " step(s)" : std::string("is not closed"));
+        return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+      }
+      ++k;
+    } }
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // (an earlier run may still read the tables that are replaced now)
-  int rc = dict_upload(c, p->dict, &T.dev);
+  bool computed = false;   // some table is COMPUTED from the packed dictionary (LENGTH / STRING_OFFSET)
+  for (auto& st : p->stages)
+    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
+      for (auto& g : pr->gathers) computed = computed || (g.join_id == JOIN_GATHER_DICT_TABLE && !is_string_producer(g.fn));
+  int rc = computed ? dict_upload(c, p->dict, &T.dev) : SSGPU_OK;
   if (rc != SSGPU_OK) return rc;
   const int32_t n = ssgpu_dict_size(p->dict);
   for (auto& st : p->stages)
     for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
       for (auto& g : pr->gathers) {
         if (g.join_id != JOIN_GATHER_DICT_TABLE) continue;
+        if (is_string_producer(g.fn)) {
+          // the table of the LAST step with this key: its domain is the largest.  An empty dictionary still gets one entry, 0.
+          DevBuf& table = T.tables[ssgpu_plan::DictTables::key(g)];
+          ssgpu_string_step want; want.fn = g.fn; want.has_len = g.has_len ? 1 : 0; want.pos = g.pos; want.len = g.len;
+          int32_t k = dict_steps - 1;
+          while (k >= 0 && !same_step(*ssgpu_dict_step(p->dict, k), want)) --k;
+          if (k < 0) { c->err = "internal: a producer table without its step"; return SSGPU_ERROR_UNKNOWN; }
+          HIP_TRY(c, table.ensure((size_t)std::max<int32_t>(n, 1) * 4));
+          if (n) HIP_TRY(c, hipMemcpyAsync(table.p, ssgpu_dict_step_table_data(p->dict, k), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+          else HIP_TRY(c, hipMemsetAsync(table.p, 0, 4, c->stream));
+          continue;
+        }
         const char* needle = ""; int32_t nlen = 0;
         if (g.fn == 476 && ssgpu_dict_decode(p->dict, g.needle_code, &needle, &nlen) != SSGPU_OK) {
           c->err = "STRING_OFFSET: the needle's code " + std::to_string(g.needle_code) + " is outside the plan's dictionary of " + std::to_string(n) + " values (ssgpu_plan_set_dict)";
           return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
         }
-        rc = dict_table_build(c, T.dev, g.fn, needle, (uint32_t)nlen, g.fold, &T.needle, &T.tables[std::make_tuple(g.fn, g.needle_code, g.fold)]);
+        rc = dict_table_build(c, T.dev, g.fn, needle, (uint32_t)nlen, g.fold, &T.needle, &T.tables[ssgpu_plan::DictTables::key(g)]);
         if (rc != SSGPU_OK) return rc;
         p->counters.n_launches += 1;
       }
@@ -1357,7 +1436,7 @@ void apply_joins(const ssgpu_plan* p, const StageExec& ex, const Program& prog, 
   for (size_t g = 0; g < prog.gathers.size() && g < VM_MAX_JOIN_COLS; ++g) {
     const JoinGather& jg = prog.gathers[g];
     if (jg.join_id == JOIN_GATHER_DICT_TABLE) {   // a table over the STRING dictionary, indexed by a code (ensure_dict_tables)
-      auto it = p->dict_tables.tables.find(std::make_tuple(jg.fn, jg.needle_code, jg.fold));
+      auto it = p->dict_tables.tables.find(ssgpu_plan::DictTables::key(jg));
       P->join_cols[g].data = it != p->dict_tables.tables.end() ? it->second.p : nullptr; P->join_cols[g].is_null = nullptr;
       continue;
     }
@@ -4515,6 +4594,112 @@ int ssgpu_dict_eval(ssgpu_ctx* c, const ssgpu_dict* d, int32_t fn, const char* n
   }
   return SSGPU_OK;
 }
+int32_t ssgpu_plan_string_steps(const ssgpu_plan* p, ssgpu_string_step* out, int32_t cap) {
+  if (!p) return 0;
+  std::vector<ssgpu_string_step> steps;
+  plan_string_steps(p, &steps);
+  for (size_t i = 0; out && i < steps.size() && (int64_t)i < (int64_t)cap; ++i) out[i] = steps[i];
+  return (int32_t)steps.size();
+}
+
+// The closed dictionary (ssgpu.h): D_k = D_(k-1) U f_k(D_(k-1)), one step after the other on the device.  A step's domain is D_(k-1)'s
+// values followed by their images -- one (lengths, heap) pair of 2n rows: the length pass (string_map_kernels.hip), the scan, D_(k-1)'s
+// bytes copied to the front of the domain's heap and the write pass behind them -- and goes through the block encoder's chain
+// (encode_domain): the sorted distinct values are D_k, packed on the device as the next step's input, the first n codes are the
+// step's remap (D_(k-1) code -> D_k code) and the second n its table in D_k codes.  After the last step the compose kernel carries
+// every (remap, table) pair through the later remaps into D_final's codes, last step first; what it leaves for step 1 is base's remap.
+int ssgpu_dict_close(ssgpu_ctx* c, const ssgpu_dict* base, const ssgpu_string_step* steps, int32_t n_steps, ssgpu_dict** out, int32_t* remap) {
+  if (!c) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  if (c->device < 0) { c->err = "no gfx950 device bound to this context (bind-only context)"; return SSGPU_ERROR_NO_DEVICE; }
+  const uint64_t n0 = base ? (uint64_t)ssgpu_dict_size(base) : 0;
+  if (!base || !out || n_steps < 0 || (n_steps > 0 && !steps) || (n0 > 0 && !remap)) { c->err = "ssgpu_dict_close: a dictionary, its steps, and room for the dictionary and the remap"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  for (int32_t k = 0; k < n_steps; ++k) {
+    const int fn = steps[k].fn;
+    if (!is_string_producer(fn) && fn != 420) { c->err = "ssgpu_dict_close: step " + std::to_string(k) + " is no string-producing function (404 / 408 / 412 / 416 / 420 / 427)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  }
+  if (n_steps == 0) return ssgpu_dict_extend(base, nullptr, nullptr, 0, out, remap);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const bool timed = c->debug_timing != 0;   // development: where a step's time goes, on stderr (tools/string_map_bench.py)
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  DictDevice cur[2];
+  int rc = dict_upload(c, base, &cur[0]);
+  if (rc != SSGPU_OK) return rc;
+  std::deque<DevBuf> codes;              // per step: 2 x n_(k-1) codes of D_k
+  std::vector<uint64_t> n_in(1, n0);     // n_in[k] = |D_k|
+  std::vector<uint64_t> off_h;
+  std::vector<char> heap_h;
+  for (int32_t k = 0; k < n_steps; ++k) {
+    const DictDevice& in = cur[k & 1];
+    DictDevice& next = cur[(k + 1) & 1];
+    const uint64_t n = in.n;
+    if (2 * n > (uint64_t)kMaxStringDomain) { c->err = "ssgpu_dict_close: more than 2^29 values in a step's dictionary"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
+    codes.emplace_back();
+    DevBuf& kc = codes.back();
+    DevBuf lens, src, dheap, dnull, partials;
+    HIP_TRY(c, kc.ensure(std::max<uint64_t>(2 * n, 1) * 4));
+    HIP_TRY(c, lens.ensure((2 * n + 1) * 8));
+    HIP_TRY(c, src.ensure(std::max<uint64_t>(n, 1) * 8));
+    HIP_TRY(c, dnull.ensure(std::max<uint64_t>(2 * n, 1)));
+    HIP_TRY(c, partials.ensure(ssgpu_str_scan_partials(2 * n) * 8));
+    const auto t0 = now();
+    const int fn = steps[k].fn;
+    HIP_TRY(c, ssgpu_launch_str_map_len(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), n, fn, steps[k].has_len ? 1 : 0, steps[k].pos, steps[k].len,
+                                        lens.as<uint64_t>(), src.as<uint64_t>(), s));
+    HIP_TRY(c, ssgpu_launch_str_scan(lens.as<uint64_t>(), 2 * n, partials.as<uint64_t>(), s));
+    uint64_t ends[2] = {0, 0};             // the domain's heap: D_(k-1)'s bytes end at ends[0], the images at ends[1]
+    HIP_TRY(c, hipMemcpyAsync(&ends[0], lens.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&ends[1], lens.as<uint64_t>() + 2 * n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, dheap.ensure(ends[1] + 8));
+    if (ends[0]) HIP_TRY(c, hipMemcpyAsync(dheap.p, in.heap.p, ends[0], hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, ssgpu_launch_str_map_write(in.heap.as<const uint8_t>(), src.as<const uint64_t>(), lens.as<const uint64_t>() + n, n, fn == 416 ? 1 : fn == 420 ? 2 : 0,
+                                          dheap.as<uint8_t>(), s));
+    HIP_TRY(c, hipMemsetAsync(dnull.p, 0, std::max<uint64_t>(2 * n, 1), s));
+    if (timed) HIP_TRY(c, hipStreamSynchronize(s));
+    const auto t1 = now();
+    uint32_t D = 0;
+    rc = encode_domain(c, s, dheap.as<uint8_t>(), lens.as<uint64_t>(), true, dnull.as<uint8_t>(), 2 * n, {{kc.as<int32_t>(), 0, 2 * n}}, STRFN_HEAP_PAD, &off_h, &heap_h, &D,
+                       next.offs, next.heap);
+    if (rc != SSGPU_OK) return rc;
+    if (n == 0) {   // an empty dictionary stays empty: give the next step the packed form of nothing
+      HIP_TRY(c, next.offs.ensure(8)); HIP_TRY(c, next.heap.ensure(STRFN_HEAP_PAD));
+      HIP_TRY(c, hipMemsetAsync(next.offs.p, 0, 8, s)); HIP_TRY(c, hipMemsetAsync(next.heap.p, 0, STRFN_HEAP_PAD, s));
+      HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    next.n = D;
+    n_in.push_back(D);
+    if (timed) fprintf(stderr, "[ssgpu dict_close] step %d fn %d values %llu -> %u map_ms %.4f encode_ms %.4f\n", k, fn, (unsigned long long)n, D, ms(t0, t1), ms(t1, now()));
+  }
+  // compose, last step first: `later` maps D_k's codes to D_final's (nothing for the last step); the step leaves D_(k-1)'s in `to_final`
+  const uint64_t n_final = n_in[(size_t)n_steps];
+  DevBuf tables, to_final[2];
+  HIP_TRY(c, tables.ensure(std::max<uint64_t>(n_final * (uint64_t)n_steps, 1) * 4));
+  HIP_TRY(c, hipMemsetAsync(tables.p, 0, std::max<uint64_t>(n_final * (uint64_t)n_steps, 1) * 4, s));
+  const auto t2 = now();
+  for (int32_t k = n_steps - 1; k >= 0; --k) {
+    const uint64_t n = n_in[(size_t)k];
+    DevBuf& mine = to_final[k & 1];
+    HIP_TRY(c, mine.ensure(std::max<uint64_t>(n, 1) * 4));
+    const int32_t* later = k == n_steps - 1 ? nullptr : to_final[(k + 1) & 1].as<int32_t>();
+    HIP_TRY(c, ssgpu_launch_str_map_compose(codes[(size_t)k].as<int32_t>(), n, later, n_in[(size_t)k + 1], n_final, mine.as<int32_t>(),
+                                            tables.as<int32_t>() + (uint64_t)k * n_final, s));
+  }
+  std::vector<int32_t> tables_h((size_t)(n_final * (uint64_t)n_steps));
+  if (!tables_h.empty()) HIP_TRY(c, hipMemcpyAsync(tables_h.data(), tables.p, tables_h.size() * 4, hipMemcpyDeviceToHost, s));
+  if (n0) HIP_TRY(c, hipMemcpyAsync(remap, to_final[0].p, n0 * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (timed) fprintf(stderr, "[ssgpu dict_close] compose_ms %.4f\n", ms(t2, now()));
+  // (off_h / heap_h: the last step's distinct values, as the encoder copied them back)
+  ssgpu_dict* d = nullptr;
+  rc = ssgpu_dict_create_sorted(heap_h.data(), off_h.data(), (int64_t)n_final, &d);
+  if (rc != SSGPU_OK) { c->err = "ssgpu_dict_close: too many distinct values"; return rc; }
+  ssgpu_dict_set_steps(d, steps, n_steps, tables_h.data());
+  *out = d;
+  return SSGPU_OK;
+}
+
 const ssgpu_dict* ssgpu_result_column_dict(ssgpu_result* r, int32_t i) {
   if (!r || !r->plan || !concat_of(r->plan, i)) return nullptr;
   if ((size_t)i >= r->concat_dicts.size() || !r->concat_dicts[i]) { const void* d; const uint8_t* z; if (ssgpu_result_column(r, i, &d, &z) != SSGPU_OK) return nullptr; }

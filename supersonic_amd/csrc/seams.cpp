@@ -112,6 +112,9 @@ void ssgpu_allocator_free(ssgpu_allocator* a, void* p) {
 // ---- order-preserving dictionary ---------------------------------------------------------------------------------
 struct ssgpu_dict {
   std::vector<std::string> values;                  // sorted: memcmp, then length == std::string's operator< on bytes
+  // a CLOSED dictionary (ssgpu_dict_close): the step list it was closed under and, per step, T_k[code(v)] = code(f_k(v)) over its own codes
+  std::vector<ssgpu_string_step> steps;
+  std::vector<std::vector<int32_t>> step_tables;
   // value -> code, built on first use: a dictionary made on the device for a block is often only decoded, never looked up
   const std::unordered_map<std::string, int32_t>& codes() const {
     std::call_once(code_once, [this] { code.reserve(values.size()); for (size_t i = 0; i < values.size(); ++i) code[values[i]] = (int32_t)i; });
@@ -185,6 +188,24 @@ int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offsets, int64_t 
   d->values.reserve((size_t)n);
   for (int64_t i = 0; i < n; ++i) d->values.emplace_back(heap + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
   *out = d;
+  return SSGPU_OK;
+}
+
+// internal (runtime.cpp: ssgpu_dict_close): makes `d` a closed dictionary -- `tables` holds n tables of ssgpu_dict_size(d) entries, one after the other
+void ssgpu_dict_set_steps(ssgpu_dict* d, const ssgpu_string_step* steps, int32_t n, const int32_t* tables) {
+  const size_t size = d->values.size();
+  d->steps.assign(steps, steps + n);
+  d->step_tables.resize((size_t)n);
+  for (int32_t k = 0; k < n; ++k) d->step_tables[(size_t)k].assign(tables + (size_t)k * size, tables + ((size_t)k + 1) * size);
+}
+// ... and reads them back: the step count, steps[k] and T_k (ensure_dict_tables uploads it)
+int32_t ssgpu_dict_step_count(const ssgpu_dict* d) { return d ? (int32_t)d->steps.size() : 0; }
+const ssgpu_string_step* ssgpu_dict_step(const ssgpu_dict* d, int32_t k) { return d && k >= 0 && (size_t)k < d->steps.size() ? &d->steps[(size_t)k] : nullptr; }
+const int32_t* ssgpu_dict_step_table_data(const ssgpu_dict* d, int32_t k) { return d && k >= 0 && (size_t)k < d->step_tables.size() ? d->step_tables[(size_t)k].data() : nullptr; }
+
+int ssgpu_dict_step_table(const ssgpu_dict* d, int32_t k, int32_t* out_host) {
+  if (!d || k < 0 || (size_t)k >= d->step_tables.size() || (!out_host && !d->values.empty())) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  if (!d->values.empty()) memcpy(out_host, d->step_tables[(size_t)k].data(), d->values.size() * sizeof(int32_t));
   return SSGPU_OK;
 }
 
