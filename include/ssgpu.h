@@ -442,6 +442,14 @@ int ssgpu_dict_eval(ssgpu_ctx* ctx, const ssgpu_dict* d, int32_t fn, const char*
  * INT64 (FLOAT / DOUBLE: type mismatch; a value that varies per row: ERROR_NOT_IMPLEMENTED at bind -- one table per (function, pos,
  * len) is the mechanism); a NULL pos / len gives an all-NULL result and needs no table.  The result is STRING, NULL iff an argument is.
  * TO_LOWER (420) as a value is still refused at bind (the kernels take the fold direction as a parameter: lifting it is a binder change).
+ *   OPERATOR_STRING_REPLACE = 480, 3 arguments STRING_REPLACE(x, needle, substitute) (string_evaluators.h:76-90, util.cc:201-222 with
+ *                                  replace_all): every occurrence of needle, leftmost first and non-overlapping ("aaaaa", "aa" -> "b" is
+ *                                  "bba"), replaced by substitute, which is never searched again; bytes are bytes (no folding; 0x00
+ *                                  and bytes >= 0x80 are ordinary); an empty needle leaves x as it is.
+ * All three arguments are STRING (anything else: ERROR_ATTRIBUTE_TYPE_MISMATCH); needle / substitute are STRING CONSTANTS -- codes, like
+ * STRING_OFFSET's needle -- or NULL (one that varies per row: ERROR_NOT_IMPLEMENTED naming the argument; a NULL one: an all-NULL result,
+ * no table and no step).  Nothing folds at bind: the binder sees codes, never bytes, so an empty needle is a step too (its table is the
+ * identity on its domain).  The result is STRING, NULL iff an argument is.
  *
  * THE CLOSED DICTIONARY.  The result of such a node is again a code of the plan's one dictionary, so everything downstream -- comparison,
  * sort, group / join keys, MIN / MAX, CONCAT, fetch and decode, LENGTH / STRING_OFFSET on top -- works on it unchanged, and the node itself
@@ -466,12 +474,24 @@ int ssgpu_dict_eval(ssgpu_ctx* ctx, const ssgpu_dict* d, int32_t fn, const char*
  * description must be codes of the CLOSED dictionary, so a caller creates the plan, asks for its steps, closes its dictionary, emits the
  * description again and creates the plan anew.  The run uploads the dictionary's own tables -- nodes with an equal key share the table of the
  * LAST step with that key, whose domain is the largest -- and computes nothing.  Any other dictionary (none, unclosed, closed under another
- * list) fails the run with ERROR_INVALID_ARGUMENT_VALUE naming ssgpu_dict_close: a run never reads a table that is not its own. */
+ * list) fails the run with ERROR_INVALID_ARGUMENT_VALUE naming ssgpu_dict_close: a run never reads a table that is not its own.
+ *
+ * A STRING_REPLACE STEP is {fn = 480, has_len = 0, pos = the needle's code, len = the substitute's code} -- the record's layout is
+ * unchanged -- and the two codes are codes of THE DICTIONARY THE LIST IS STATED AGAINST.  ssgpu_plan_string_steps reports them as they
+ * stand in the plan description: the first plan is emitted against the base dictionary, and exactly that list goes to
+ * ssgpu_dict_close(base, ...), which reads a 480-step's pos / len as codes of `base` (a constant is a value of D_0, so both are there;
+ * a code outside [0, ssgpu_dict_size(base)) is ERROR_INVALID_ARGUMENT_VALUE naming the step -- checked after the device: a bind-only
+ * context answers ERROR_NO_DEVICE first) and resolves them to bytes once, before step 0.  The closed dictionary REMEMBERS such a step
+ * with the two codes translated into its own (remap[pos], remap[len]); the plan created anew over it bakes its constants as closed
+ * codes, so its step list matches the remembered one field by field, in the subsequence check and in the table lookup alike.  Two
+ * replace nodes share a table iff needle and substitute are equal.  Unlike the functions above the image is no slice of the value: the
+ * step has a length and a write pass of its own (string_map_kernels.hip: ssgpu_str_replace_len_kernel / _write_kernel); the scan, the
+ * encoder, the compose pass and the tables are the same. */
 typedef struct ssgpu_string_step {
-  int32_t fn;       /* 404 LTRIM, 408 RTRIM, 412 TRIM, 416 TO_UPPER, 427 SUBSTRING (ssgpu_dict_close also takes 420 TO_LOWER) */
+  int32_t fn;       /* 404 LTRIM, 408 RTRIM, 412 TRIM, 416 TO_UPPER, 427 SUBSTRING, 480 STRING_REPLACE (ssgpu_dict_close also takes 420 TO_LOWER) */
   int32_t has_len;  /* SUBSTRING: 1 = the 3-argument form */
-  int64_t pos;      /* SUBSTRING only, else 0 */
-  int64_t len;      /* SUBSTRING with has_len only, else 0 */
+  int64_t pos;      /* SUBSTRING: the position; STRING_REPLACE: the needle's code; else 0 */
+  int64_t len;      /* SUBSTRING with has_len: the length; STRING_REPLACE: the substitute's code; else 0 */
 } ssgpu_string_step;
 int32_t ssgpu_plan_string_steps(const ssgpu_plan* plan, ssgpu_string_step* out, int32_t cap);
 int ssgpu_dict_close(ssgpu_ctx* ctx, const ssgpu_dict* base, const ssgpu_string_step* steps, int32_t n, ssgpu_dict** out, int32_t* remap);

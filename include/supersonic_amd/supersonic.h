@@ -476,6 +476,11 @@ inline const Expression* Trim(const Expression* a) { return internal::Op(412, a)
 inline const Expression* ToUpper(const Expression* a) { return internal::Op(416, a); }
 inline const Expression* Substring(const Expression* str, const Expression* pos, const Expression* len) { return internal::Op(427, str, pos, len); }
 inline const Expression* TrailingSubstring(const Expression* str, const Expression* pos) { return internal::Op(427, str, pos); }
+// OPERATOR_STRING_REPLACE: every non-overlapping occurrence of `needle`, leftmost first, replaced by `substitute`; an empty needle leaves
+// the value as it is.  `needle` / `substitute` are ConstString or Null; the haystack is any STRING expression.
+inline const Expression* StringReplace(const Expression* haystack, const Expression* needle, const Expression* substitute) {
+  return internal::Op(480, haystack, needle, substitute);
+}
 // owning list of expressions (expression/base/expression.h): the arguments of Case / In
 class ExpressionList {
  public:

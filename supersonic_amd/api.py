@@ -126,11 +126,14 @@ class StringDictionary(object):
         return out
 
     LTRIM, RTRIM, TRIM, TO_UPPER, TO_LOWER, SUBSTRING = 404, 408, 412, 416, 420, 427
+    STRING_REPLACE = 480
 
     def close(self, steps, context=None):
         """ssgpu_dict_close: self closed under `steps` -- (fn,) / (fn, pos) / (fn, pos, len) tuples or ssgpu_string_step records, in
         order -- on the device -> (dictionary, remap): every step's images joined in, remap[c] the new code of code c.  The result keeps
-        its steps (.steps) and one table per step (step_table)."""
+        its steps (.steps) and one table per step (step_table).  A STRING_REPLACE step is (480, needle, substitute) with the two constants
+        as bytes -- values of self, anything else raises -- or as their codes in self (what a record carries); .steps of the result
+        reports it with the codes they have in the CLOSED dictionary."""
         ctx = context or Context.default()
         recs = (L.StringStep * max(len(steps), 1))()
         for i, st in enumerate(steps):
@@ -138,13 +141,19 @@ class StringDictionary(object):
                 recs[i] = st
                 continue
             st = tuple(st) if isinstance(st, (tuple, list)) else (st,)
+            if int(st[0]) == self.STRING_REPLACE:
+                if len(st) != 3:
+                    raise SupersonicException(L.ERROR_INVALID_ARGUMENT_VALUE, "a STRING_REPLACE step is (480, needle, substitute)")
+                recs[i] = L.StringStep(480, 0, *[self.code_of(v) if isinstance(v, (bytes, bytearray, str)) else int(v) for v in st[1:]])
+                continue
             recs[i] = L.StringStep(int(st[0]), 1 if len(st) > 2 else 0, int(st[1]) if len(st) > 1 else 0, int(st[2]) if len(st) > 2 else 0)
         remap = np.zeros(max(len(self), 1), np.int32)
         h = C.c_void_p()
         ctx.check(self.lib.ssgpu_dict_close(ctx.handle, self.handle, recs, len(steps), C.byref(h), remap.ctypes.data_as(C.POINTER(C.c_int32))))
         d = StringDictionary.__new__(StringDictionary)
         d.lib, d.handle = self.lib, h
-        d.steps = [(r.fn, r.has_len, r.pos, r.len) for r in recs[:len(steps)]]
+        d.steps = [(r.fn, 0, int(remap[r.pos]), int(remap[r.len])) if r.fn == self.STRING_REPLACE else (r.fn, r.has_len, r.pos, r.len)
+                   for r in recs[:len(steps)]]
         return d, remap[:len(self)]
 
     def step_table(self, k):
@@ -748,6 +757,7 @@ def Trim(a): return _op(412, a)
 def ToUpper(a): return _op(416, a)
 def Substring(s, pos, length): return _op(427, s, pos, length)
 def TrailingSubstring(s, pos): return _op(427, s, pos)
+def StringReplace(haystack, needle, substitute): return _op(480, haystack, needle, substitute)
 
 
 class ExpressionList(object):

@@ -30,7 +30,7 @@ enum {
   OP_ASIN = 812, OP_ACOS = 816, OP_ATAN = 820, OP_ATAN2 = 824, OP_SINH = 828, OP_COSH = 832, OP_TANH = 836, OP_ASINH = 840,
   OP_ACOSH = 844, OP_ATANH = 848,
   OP_SQRT_QUIET = 333, OP_SQRT_NULLING = 334, OP_SQRT_SIGNALING = 335, OP_CEIL = 342, OP_FLOOR = 346, OP_ABS = 360,
-  OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_TOLOWER = 420, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476,
+  OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_TOLOWER = 420, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476, OP_STRING_REPLACE = 480,
   OP_CASE = 200, OP_IF = 204, OP_IN = 208, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265
 };
 
@@ -763,6 +763,27 @@ static Status bind_operator(const ssgpu_expr& x, std::vector<BExprP> args, int d
       BExprP e = make_op(op, SSGPU_STRING, nullable, name, {args[0]}, depth);
       e->str_null = null_arg; e->str_has_len = num.size() == 2;
       if (!null_arg) { e->str_pos = bits_to_i64(SSGPU_INT64, num[0]->bits); if (e->str_has_len) e->str_len = bits_to_i64(SSGPU_INT64, num[1]->bits); }
+      *out = e;
+      return Status::OK();
+    }
+    case OP_STRING_REPLACE: {
+      // STRING_REPLACE(haystack, needle, substitute) (string_expressions_test.cc:67-68, 86): with a constant needle and substitute a
+      // function of one STRING value, so one more step of the closed dictionary.  Nothing folds here, an empty needle included: a STRING
+      // constant is a code and the binder never sees its bytes.
+      SS_RETURN_IF_ERROR(need(3));
+      for (const BExprP& a : args)
+        if (a->dtype != SSGPU_STRING)
+          return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("STRING_REPLACE needs STRING arguments, got ") + dtype_name(a->dtype) + " in " + a->name);
+      for (size_t i = 1; i < 3; ++i)
+        if (!is_constant(args[i])) {
+          const std::string what = i == 1 ? "needle" : "substitute";
+          return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "STRING_REPLACE: the " + what + " must be a STRING constant or NULL (one table per (needle, substitute) is built "
+                                                            "over the dictionary); a " + what + " that varies per row (" + args[i]->name + ") is outside the device hot path");
+        }
+      BExprP e = make_op(op, SSGPU_STRING, args[0]->nullable || args[1]->nullable || args[2]->nullable,
+                         "STRING_REPLACE(" + args[0]->name + ", " + args[1]->name + ", " + args[2]->name + ")", {args[0]}, depth);
+      e->str_null = args[1]->kind == BExpr::NULLCONST || args[2]->kind == BExpr::NULLCONST;
+      if (!e->str_null) { e->str_pos = (int64_t)(int32_t)(uint32_t)args[1]->bits; e->str_len = (int64_t)(int32_t)(uint32_t)args[2]->bits; }
       *out = e;
       return Status::OK();
     }

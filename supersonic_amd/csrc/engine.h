@@ -69,7 +69,8 @@ struct BExpr {
   uint64_t bits = 0;   // CONST: raw value bits in the column's device width
   int filter_depth = 0;  // number of Filter operations below this expression
   // string-producing OP (LTRIM 404 ... SUBSTRING 427; args = the STRING argument alone): SUBSTRING's constant position and length
-  // (str_has_len: the 3-argument form); str_null: a NULL position / length -- the result is NULL everywhere and needs no table
+  // (str_has_len: the 3-argument form); str_null: a NULL position / length -- the result is NULL everywhere and needs no table.
+  // STRING_REPLACE 480 keeps its constant needle's code in str_pos and its substitute's in str_len (str_null: one of them is NULL)
   int64_t str_pos = 0, str_len = 0;
   bool str_has_len = false, str_null = false;
   std::vector<BExprP> args;
@@ -115,14 +116,15 @@ struct JoinSpec {
 // slot i of VmParams.join_cols: a column (or NULL mask) of a join's rhs table, or -- join_id == JOIN_GATHER_DICT_TABLE -- a table
 // over the plan's STRING dictionary, indexed by a code: table[c] = fn(value c) (string_fn_kernels.hip), fn = 400 LENGTH,
 // 476 STRING_OFFSET of the value whose code is `needle_code`, compared through ascii_tolower when `fold`; or the table of a
-// string-producing function (is_string_producer(fn): 404 / 408 / 412 / 416 / 427 with SUBSTRING's pos / len / has_len), table[c] = the
+// string-producing function (is_string_producer(fn): 404 / 408 / 412 / 416 / 427 with SUBSTRING's pos / len / has_len, 480
+// STRING_REPLACE with pos = the needle's code and len = the substitute's, has_len false), table[c] = the
 // code of fn(value c) in the plan's CLOSED dictionary, which holds it (ssgpu_dict_close; runtime.cpp only uploads it)
 struct JoinGather {
   int join_id; int rhs_col; bool is_null_mask; int fn = 0; int32_t needle_code = 0; bool fold = false;
   int64_t pos = 0, len = 0; bool has_len = false;
 };
 enum { JOIN_GATHER_DICT_TABLE = -2 };
-inline bool is_string_producer(int fn) { return fn == 404 || fn == 408 || fn == 412 || fn == 416 || fn == 427; }
+inline bool is_string_producer(int fn) { return fn == 404 || fn == 408 || fn == 412 || fn == 416 || fn == 427 || fn == 480; }
 enum { JOIN_GATHER_RUN_START = -1, JOIN_GATHER_RUN_COUNT = -2 };   // rhs_col of a multi join's per-key run arrays
 
 // Lowered instruction over virtual registers.  A register is an LDS array of

@@ -349,6 +349,13 @@ hipError_t ssgpu_launch_str_map_len(const uint8_t* heap, const uint64_t* offs, u
 hipError_t ssgpu_launch_str_map_write(const uint8_t* heap, const uint64_t* src, const uint64_t* dst_offs, uint64_t n, int dir, uint8_t* out, hipStream_t s);
 hipError_t ssgpu_launch_str_map_compose(const int32_t* codes, uint64_t n, const int32_t* later, uint64_t n_later, uint64_t n_final, int32_t* to_final,
                                         int32_t* table, hipStream_t s);
+// STRING_REPLACE 480 as a closing step: the same two passes for an image that is no slice of its value.  `needle` / `sub` are small
+// device buffers (at least one byte each, whatever the lengths).  The length pass fills lens[0, n) and lens[n, 2n) as above; the write
+// pass makes the same selection of matches again and writes image i to out[dst_offs[i], dst_offs[i + 1]).  Same heap contract.
+hipError_t ssgpu_launch_str_replace_len(const uint8_t* heap, const uint64_t* offs, uint64_t n, const uint8_t* needle, uint32_t needle_len, uint32_t sub_len,
+                                        uint64_t* lens, hipStream_t s);
+hipError_t ssgpu_launch_str_replace_write(const uint8_t* heap, const uint64_t* offs, const uint64_t* dst_offs, uint64_t n, const uint8_t* needle, uint32_t needle_len,
+                                          const uint8_t* sub, uint32_t sub_len, uint8_t* out, hipStream_t s);
 hipError_t ssgpu_launch_sort_unkey(void* out, const uint64_t* keys, uint32_t width, int kind, int descending, uint64_t n, hipStream_t s);
 hipError_t ssgpu_launch_sort_gather(void* out, uint8_t* out_nulls, const void* col, const uint8_t* nulls, uint32_t width,
                                     const uint32_t* idx, uint64_t n, hipStream_t s);

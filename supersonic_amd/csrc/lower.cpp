@@ -34,7 +34,8 @@ enum {
   OP_AND_NOT = 48, OP_NOT = 52, OP_XOR = 56, OP_BITWISE_AND = 60, OP_BITWISE_OR = 64,
   OP_BITWISE_NOT = 68, OP_BITWISE_XOR = 72, OP_SHIFT_LEFT = 76, OP_SHIFT_RIGHT = 80,
   OP_BITWISE_ANDNOT = 84, OP_EQUAL = 100, OP_NOT_EQUAL = 104, OP_LESS = 116, OP_LESS_OR_EQUAL = 120,
-  OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265, OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476
+  OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265, OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476,
+  OP_STRING_REPLACE = 480
 };
 
 // machine type classes
@@ -233,7 +234,7 @@ std::string Emitter::key_of(const BExprP& e) {
     default:
       s << (e->kind == BExpr::CAST ? "K" : "O") << e->op << ":" << e->dtype << ":" << e->filter_depth;
       if (e->kind == BExpr::OP && e->op == OP_STRING_OFFSET) s << (e->bits ? "ci" : "cs");   // BExpr::bits: compared through ascii_tolower
-      if (e->kind == BExpr::OP && e->op == OP_SUBSTRING) s << "@" << e->str_pos << ":" << e->str_len << ":" << e->str_has_len << e->str_null;
+      if (e->kind == BExpr::OP && (e->op == OP_SUBSTRING || e->op == OP_STRING_REPLACE)) s << "@" << e->str_pos << ":" << e->str_len << ":" << e->str_has_len << e->str_null;
       s << "(";
       for (auto& a : e->args) s << key_of(a) << ",";
       s << ")";
@@ -586,12 +587,13 @@ Status Emitter::value(const BExprP& e, Val* out) {
           LInstr& i = emit(VM_GATHER_32); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot;
           v.null = a[0].null;
         } break;
-        case OP_LTRIM: case OP_RTRIM: case OP_TRIM: case OP_TOUPPER: case OP_SUBSTRING: {
+        case OP_LTRIM: case OP_RTRIM: case OP_TRIM: case OP_TOUPPER: case OP_SUBSTRING: case OP_STRING_REPLACE: {
           // f(s) = T[code(s)] again, with T[c] = the code of f(value c): the plan's dictionary is closed under the plan's producer
           // nodes (ssgpu_dict_close), so the result is a code of the same dictionary and everything above works on it as on a column.
           // Every entry of T is a valid code, so a nested producer gathers with whatever this one read.  The node joins the
           // program's step list here -- after its argument: post-order.
-          if (e->str_null) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // NULL position / length
+          // STRING_REPLACE's step carries the codes of its constant needle and substitute in pos / len.
+          if (e->str_null) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // NULL position / length / needle / substitute
           const int code = materialize(a[0]);
           const int slot = producer_slot(e->op, e->str_pos, e->str_len, e->str_has_len);
           ssgpu_string_step step; step.fn = e->op; step.has_len = e->str_has_len ? 1 : 0; step.pos = e->str_pos; step.len = e->str_len;

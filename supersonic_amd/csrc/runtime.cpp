@@ -1121,7 +1121,8 @@ const char* ssgpu_plan_describe(ssgpu_plan* p) {
       for (auto& g : pr->gathers) {
         if (g.join_id != JOIN_GATHER_DICT_TABLE || !seen.insert(ssgpu_plan::DictTables::key(g)).second) continue;
         if (is_string_producer(g.fn)) {
-          lines += std::string("dictionary table: ") + (g.fn == 404 ? "LTRIM" : g.fn == 408 ? "RTRIM" : g.fn == 412 ? "TRIM" : g.fn == 416 ? "TO_UPPER" : "SUBSTRING");
+          lines += std::string("dictionary table: ") + (g.fn == 404 ? "LTRIM" : g.fn == 408 ? "RTRIM" : g.fn == 412 ? "TRIM" : g.fn == 416 ? "TO_UPPER" : g.fn == 480 ? "STRING_REPLACE" : "SUBSTRING");
+          if (g.fn == 480) lines += " needle code " + std::to_string(g.pos) + " substitute code " + std::to_string(g.len);
           if (g.fn == 427) lines += " position " + std::to_string(g.pos) + (g.has_len ? " length " + std::to_string(g.len) : std::string(" to the end"));
           lines += " (codes of the closed dictionary)\n";
           continue;
@@ -1353,6 +1354,7 @@ static void plan_string_steps(const ssgpu_plan* p, std::vector<ssgpu_string_step
       out->insert(out->end(), pr->string_steps.begin(), pr->string_steps.end());
 }
 static bool same_step(const ssgpu_string_step& a, const ssgpu_string_step& b) {
+  if (a.fn == 480) return b.fn == 480 && a.pos == b.pos && a.len == b.len;   // needle and substitute: codes of the same dictionary
   return a.fn == b.fn && (a.fn != 427 || (a.pos == b.pos && (a.has_len != 0) == (b.has_len != 0) && (!a.has_len || a.len == b.len)));
 }
 static bool plan_has_dict_tables(const ssgpu_plan* p) {
@@ -1369,7 +1371,7 @@ int ensure_dict_tables(ssgpu_plan* p) {
     std::vector<ssgpu_string_step> producers;
     plan_string_steps(p, &producers);
     c->err = producers.empty() ? "LENGTH / STRING_OFFSET of a STRING value need the plan's dictionary (ssgpu_plan_set_dict)"
-                               : "LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING need the plan's dictionary, closed under the plan's steps (ssgpu_plan_string_steps, "
+                               : "LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING / STRING_REPLACE need the plan's dictionary, closed under the plan's steps (ssgpu_plan_string_steps, "
                                  "ssgpu_dict_close, ssgpu_plan_set_dict)";
     return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
   }
@@ -1386,7 +1388,7 @@ int ensure_dict_tables(ssgpu_plan* p) {
     for (const ssgpu_string_step& s : steps) {
       while (k < dict_steps && !same_step(*ssgpu_dict_step(p->dict, k), s)) ++k;
       if (k == dict_steps) {
-        c->err = std::string("LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING make STRING values: the plan's dictionary must be closed under the plan's ") +
+        c->err = std::string("LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING / STRING_REPLACE make STRING values: the plan's dictionary must be closed under the plan's ") +
                  std::to_string(steps.size()) + " step(s) (ssgpu_plan_string_steps, ssgpu_dict_close, ssgpu_plan_set_dict); this one " +
                  (dict_steps ? "was closed under another list of " + std::to_string(dict_steps) + " step(s)" : std::string("is not closed"));
         return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
@@ -4615,7 +4617,21 @@ int ssgpu_dict_close(ssgpu_ctx* c, const ssgpu_dict* base, const ssgpu_string_st
   if (!base || !out || n_steps < 0 || (n_steps > 0 && !steps) || (n0 > 0 && !remap)) { c->err = "ssgpu_dict_close: a dictionary, its steps, and room for the dictionary and the remap"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
   for (int32_t k = 0; k < n_steps; ++k) {
     const int fn = steps[k].fn;
-    if (!is_string_producer(fn) && fn != 420) { c->err = "ssgpu_dict_close: step " + std::to_string(k) + " is no string-producing function (404 / 408 / 412 / 416 / 420 / 427)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+    if (!is_string_producer(fn) && fn != 420) { c->err = "ssgpu_dict_close: step " + std::to_string(k) + " is no string-producing function (404 / 408 / 412 / 416 / 420 / 427 / 480)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  }
+  // STRING_REPLACE: a step's pos / len are the codes of its needle / substitute in `base` -- constants of the plan, so values of D_0 -- and
+  // are resolved to bytes once, here; the closed dictionary remembers the step with the two codes in ITS codes (below)
+  std::vector<std::pair<std::string, std::string>> replace_bytes((size_t)n_steps);
+  for (int32_t k = 0; k < n_steps; ++k) {
+    if (steps[k].fn != 480) continue;
+    const char* nb = nullptr; const char* sb = nullptr; int32_t nl = 0, sl = 0;
+    if (steps[k].pos < 0 || steps[k].pos >= (int64_t)n0 || steps[k].len < 0 || steps[k].len >= (int64_t)n0 ||
+        ssgpu_dict_decode(base, (int32_t)steps[k].pos, &nb, &nl) != SSGPU_OK || ssgpu_dict_decode(base, (int32_t)steps[k].len, &sb, &sl) != SSGPU_OK) {
+      c->err = "ssgpu_dict_close: step " + std::to_string(k) + " (STRING_REPLACE): needle code " + std::to_string(steps[k].pos) + " / substitute code " +
+               std::to_string(steps[k].len) + " outside the base dictionary of " + std::to_string(n0) + " values";
+      return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+    }
+    replace_bytes[(size_t)k] = {std::string(nb, (size_t)nl), std::string(sb, (size_t)sl)};
   }
   if (n_steps == 0) return ssgpu_dict_extend(base, nullptr, nullptr, 0, out, remap);
   HIP_TRY(c, hipSetDevice(c->device));
@@ -4645,8 +4661,19 @@ int ssgpu_dict_close(ssgpu_ctx* c, const ssgpu_dict* base, const ssgpu_string_st
     HIP_TRY(c, partials.ensure(ssgpu_str_scan_partials(2 * n) * 8));
     const auto t0 = now();
     const int fn = steps[k].fn;
-    HIP_TRY(c, ssgpu_launch_str_map_len(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), n, fn, steps[k].has_len ? 1 : 0, steps[k].pos, steps[k].len,
-                                        lens.as<uint64_t>(), src.as<uint64_t>(), s));
+    const std::string& needle = replace_bytes[(size_t)k].first;
+    const std::string& sub = replace_bytes[(size_t)k].second;
+    DevBuf needle_dev, sub_dev;
+    if (fn == 480) {
+      HIP_TRY(c, needle_dev.ensure(std::max<size_t>(needle.size(), 1))); HIP_TRY(c, sub_dev.ensure(std::max<size_t>(sub.size(), 1)));
+      if (!needle.empty()) HIP_TRY(c, hipMemcpyAsync(needle_dev.p, needle.data(), needle.size(), hipMemcpyHostToDevice, s));
+      if (!sub.empty()) HIP_TRY(c, hipMemcpyAsync(sub_dev.p, sub.data(), sub.size(), hipMemcpyHostToDevice, s));
+      HIP_TRY(c, ssgpu_launch_str_replace_len(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), n, needle_dev.as<const uint8_t>(), (uint32_t)needle.size(),
+                                              (uint32_t)sub.size(), lens.as<uint64_t>(), s));
+    } else {
+      HIP_TRY(c, ssgpu_launch_str_map_len(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), n, fn, steps[k].has_len ? 1 : 0, steps[k].pos, steps[k].len,
+                                          lens.as<uint64_t>(), src.as<uint64_t>(), s));
+    }
     HIP_TRY(c, ssgpu_launch_str_scan(lens.as<uint64_t>(), 2 * n, partials.as<uint64_t>(), s));
     uint64_t ends[2] = {0, 0};             // the domain's heap: D_(k-1)'s bytes end at ends[0], the images at ends[1]
     HIP_TRY(c, hipMemcpyAsync(&ends[0], lens.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
@@ -4654,8 +4681,12 @@ int ssgpu_dict_close(ssgpu_ctx* c, const ssgpu_dict* base, const ssgpu_string_st
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, dheap.ensure(ends[1] + 8));
     if (ends[0]) HIP_TRY(c, hipMemcpyAsync(dheap.p, in.heap.p, ends[0], hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, ssgpu_launch_str_map_write(in.heap.as<const uint8_t>(), src.as<const uint64_t>(), lens.as<const uint64_t>() + n, n, fn == 416 ? 1 : fn == 420 ? 2 : 0,
-                                          dheap.as<uint8_t>(), s));
+    if (fn == 480)
+      HIP_TRY(c, ssgpu_launch_str_replace_write(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), lens.as<const uint64_t>() + n, n, needle_dev.as<const uint8_t>(),
+                                                (uint32_t)needle.size(), sub_dev.as<const uint8_t>(), (uint32_t)sub.size(), dheap.as<uint8_t>(), s));
+    else
+      HIP_TRY(c, ssgpu_launch_str_map_write(in.heap.as<const uint8_t>(), src.as<const uint64_t>(), lens.as<const uint64_t>() + n, n, fn == 416 ? 1 : fn == 420 ? 2 : 0,
+                                            dheap.as<uint8_t>(), s));
     HIP_TRY(c, hipMemsetAsync(dnull.p, 0, std::max<uint64_t>(2 * n, 1), s));
     if (timed) HIP_TRY(c, hipStreamSynchronize(s));
     const auto t1 = now();
@@ -4695,7 +4726,11 @@ int ssgpu_dict_close(ssgpu_ctx* c, const ssgpu_dict* base, const ssgpu_string_st
   ssgpu_dict* d = nullptr;
   rc = ssgpu_dict_create_sorted(heap_h.data(), off_h.data(), (int64_t)n_final, &d);
   if (rc != SSGPU_OK) { c->err = "ssgpu_dict_close: too many distinct values"; return rc; }
-  ssgpu_dict_set_steps(d, steps, n_steps, tables_h.data());
+  // a STRING_REPLACE step is remembered with its two constants as codes of THIS dictionary: the plan created anew over it bakes them so
+  std::vector<ssgpu_string_step> kept(steps, steps + n_steps);
+  for (ssgpu_string_step& st : kept)
+    if (st.fn == 480) { st.has_len = 0; st.pos = remap[st.pos]; st.len = remap[st.len]; }
+  ssgpu_dict_set_steps(d, kept.data(), n_steps, tables_h.data());
   *out = d;
   return SSGPU_OK;
 }

@@ -1,10 +1,10 @@
-"""String-producing functions (Trim / ToUpper / Substring): what closing a dictionary costs, and what a row pays afterwards.
+"""String-producing functions (Trim / ToUpper / Substring / StringReplace): what closing a dictionary costs, and what a row pays afterwards.
 
-Closing: D distinct values of 12..40 bytes, a third of them with 1..3 trailing spaces.  StringDictionary.close under ONE step, TRIM
-and TO_UPPER, by the host clock (it includes packing and uploading the dictionary, the copy of the distinct bytes back and the new
+Closing: D distinct values of 12..40 bytes, a third of them with 1..3 trailing spaces.  StringDictionary.close under ONE step, TRIM,
+TO_UPPER and STRING_REPLACE("cd" -> "D"; the two constants join the dictionary, as a plan's would), by the host clock (it includes packing and uploading the dictionary, the copy of the distinct bytes back and the new
 host dictionary) and, from the context's debug_timing lines, the step's two parts: the image kernels (length pass, scan, copy of
 the base bytes, write pass) and the re-encode of the 2n-row domain (hash, insert, compact, sort, rank, codes, gather and the copy
-back) -- against the images computed on the host by a single-threaded loop: CPython, one bytes.rstrip / bytes.upper per value over
+back) -- against the images computed on the host by a single-threaded loop: CPython, one bytes.strip / bytes.upper / bytes.replace per value over
 the packed heap (the images only: no sort, no codes).
 Per-row cost: ROWS rows of codes of a 1e5-value dictionary, GROUP BY TRIM(s) against GROUP BY s with COUNT(*), alternating; the
 run's time is the host clock around run + fetch (a device synchronise).  Writes one JSON document.
@@ -25,7 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import supersonic_amd as ss  # noqa: E402
 from string_fn_bench import Stderr, dictionary_of, make_values, stats  # noqa: E402
 
-TRIM, TO_UPPER = 412, 416
+TRIM, TO_UPPER, STRING_REPLACE = 412, 416, 480
+NEEDLE, SUBSTITUTE = b"cd", b"D"
 
 
 def note(text):
@@ -50,6 +51,8 @@ def host_images(heap, offs, fn):
     t0 = time.perf_counter()
     if fn == TRIM:
         out = [big[o[i]:o[i + 1]].strip(b" ") for i in range(len(o) - 1)]
+    elif fn == STRING_REPLACE:
+        out = [big[o[i]:o[i + 1]].replace(NEEDLE, SUBSTITUTE) for i in range(len(o) - 1)]
     else:
         out = [big[o[i]:o[i + 1]].upper() for i in range(len(o) - 1)]
     return out, time.perf_counter() - t0
@@ -60,8 +63,10 @@ def bench_close(ctx, n, reps):
     d = dictionary_of(heap, offs)
     out = {"distinct": n, "heap_bytes": int(offs[-1]), "steps": {}}
     ctx.set_option("debug_timing", 1)
-    for name, fn in (("TRIM", TRIM), ("TO_UPPER", TO_UPPER)):
+    with_consts, _remap = d.extend([NEEDLE, SUBSTITUTE])   # a replace step's constants are values of the dictionary it closes
+    for name, fn in (("TRIM", TRIM), ("TO_UPPER", TO_UPPER), ("STRING_REPLACE", STRING_REPLACE)):
         note("closing %d values under %s" % (n, name))
+        base, step = (with_consts, (fn, NEEDLE, SUBSTITUTE)) if fn == STRING_REPLACE else (d, (fn,))
         images, host_s = host_images(heap, offs, fn)
         new_values = len(set(images)) if n <= 1000000 else None
         del images
@@ -69,12 +74,12 @@ def bench_close(ctx, n, reps):
         for r in range(reps + 1):                          # the first call warms the code objects and the allocations
             with Stderr() as err:
                 t0 = time.perf_counter()
-                closed, remap = d.close([(fn,)], ctx)
+                closed, remap = base.close([step], ctx)
                 dt = time.perf_counter() - t0
             m = re.search(r"values (\d+) -> (\d+) map_ms ([0-9.]+) encode_ms ([0-9.]+)", err.text)
-            assert m and int(m.group(1)) == n, err.text
+            assert m and int(m.group(1)) == len(base), err.text
             size = len(closed)
-            assert size == int(m.group(2)) and len(remap) == n
+            assert size == int(m.group(2)) and len(remap) == len(base)
             del closed
             if r:
                 maps.append(float(m.group(3)))
@@ -85,7 +90,7 @@ def bench_close(ctx, n, reps):
                               "image_kernels_ms": mk, "reencode_2n_rows_ms": ek, "close_call_ms": ck,
                               "reencode_share_of_call": ek["median"] / ck["median"], "image_kernels_share_of_call": mk["median"] / ck["median"],
                               "host_side_rest_ms": ck["median"] - mk["median"] - ek["median"],
-                              "host_loop": "CPython, single thread: bytes.strip(b' ') / bytes.upper() per value over the packed heap (images only)",
+                              "host_loop": "CPython, single thread: bytes.strip(b' ') / bytes.upper() / bytes.replace(b'cd', b'D') per value over the packed heap (images only)",
                               "host_loop_ms": host_s * 1e3, "host_loop_over_image_kernels": host_s * 1e3 / mk["median"]}
     ctx.set_option("debug_timing", 0)
     return out
