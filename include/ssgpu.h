@@ -432,6 +432,45 @@ const ssgpu_dict* ssgpu_result_column_dict(ssgpu_result* r, int32_t col);
 int ssgpu_dict_eval(ssgpu_ctx* ctx, const ssgpu_dict* d, int32_t fn, const char* needle, int32_t needle_len, int32_t fold_case,
                     int32_t* out_host);
 
+/* PARSE_STRING: a STRING turned into a number (elementary_expressions.h:39-44), as SSGPU_EXPR_OP with one child and the node's `dtype`
+ * field -- the field CONST / NULL / CAST use -- as the TARGET TYPE:
+ *   OPERATOR_PARSE_STRING_QUIET = 437    NULL iff the argument is (nullable iff it is); a parse that fails yields the value stated below
+ *   OPERATOR_PARSE_STRING_NULLING = 438  NULL where the argument is NULL or the parse fails; always nullable
+ * Both are named PARSE_STRING(<child>).  Target STRING: the argument itself, under its own name.  Targets DATE, DATETIME and BINARY:
+ * ERROR_NOT_IMPLEMENTED at bind, naming the type.  An argument that is no STRING: ERROR_ATTRIBUTE_TYPE_MISMATCH.  A STRING constant is
+ * a code like any other value; a NULL constant gives an all-NULL result of the target type and needs no table.
+ * What is parsed is the value CUT AT ITS FIRST 0x00 BYTE (the reference parses input.as_string().c_str()); call it s.  isspace is
+ * the six bytes ' ' \t \n \v \f \r (bytes >= 0x80 are not space).
+ *   INT32 / UINT32 / INT64 / UINT64 (safe_strto*, base 10): isspace is stripped from both ends (nothing left: failure, value 0); one
+ *     optional '-' or '+' (nothing behind it: failure, 0; no space is skipped behind it; '-' on an unsigned target: failure, 0, "-0" too);
+ *     every further byte must be 0-9, and the first that is not is a failure whose value is the conversion of the digits in front of
+ *     it ("125 OOPS": 125, "OOPS 125": 0, "12 3": 12); overflow is a failure with value max, underflow with value min; the limits
+ *     themselves parse; leading zeros are digits (no octal, no hex).
+ *   BOOL: ' ', \t, \r (these three only) are stripped from both ends, then true / yes / false / no in any case (A-Z only); anything
+ *     else fails ("1" too).  The reference leaves a failed Quiet BOOL uninitialised; HERE IT IS false.
+ *   DOUBLE / FLOAT (safe_strtod / safe_strtof): glibc strtod / strtof in the C locale, then trailing isspace; the parse succeeds iff s
+ *     is not empty and everything was consumed, and the value is what strtod returned EVEN WHEN IT FAILS ("1.OOPS": 1.0, "--12": 0.0);
+ *     range errors are no failures (+-inf, a denormal, 0); inf, infinity, nan, nan(...), hex floats, "-1.", ".5", "1e5" are valid.
+ * A value is a code, so parse(s) = V[code(s)] and "it failed" = F[code(s)]: per TARGET TYPE one table V of 1 / 4 / 8-byte entries and
+ * one of failure bytes F are built over the plan's dictionary before the first run and again after ssgpu_plan_set_dict
+ * (string_parse_kernels.hip).  Both sit in ONE of the pipeline's 24 gather slots -- 437 and 438 of one type share it -- V as the slot's
+ * data (GATHER_8 / _32 / _64 by the code), F as its NULL mask (GATHER_NULL, only Nulling reads it).  A closed dictionary is a dictionary
+ * like any other: PARSE_STRING(TRIM(s)) gathers by TRIM's codes.  A run without a dictionary fails with ERROR_INVALID_ARGUMENT_VALUE
+ * naming PARSE_STRING.
+ * The device decides the integer and BOOL targets alone.  Of DOUBLE / FLOAT it computes the EXACT FAST PATH only --
+ *   isspace* [+-]? digits* ('.' digits*)? ([eE] [+-]? digit{1,4})? isspace*, a mantissa digit, at most 19 significant digits (leading
+ *   zeros dropped), at most 64 bytes from the first byte behind the sign that is not '0' to the end of the trimmed value, and for DOUBLE
+ *   mantissa <= 2^53 with exponent - fraction digits in [-22, 22], for FLOAT mantissa <= 2^24 and that exponent in [-10, 10]
+ * -- where one correctly rounded multiply or divide of two exact numbers is strtod's answer, and leaves every other value but the
+ * empty one (a failure with value 0) to the host: strtod / strtof on the dictionary's own bytes, once per such DISTINCT value, before
+ * the first run.  The device never decides that a floating parse failed.  ssgpu_plan_describe names every parse table and, once the
+ * tables are built, how many entries of the plan's floating tables the host resolved.
+ *
+ * ssgpu_dict_parse computes the two tables without a plan: out_values_host receives ssgpu_dict_size(d) entries of to_type's width (1, 4
+ * or 8 bytes), out_failed_host one byte per value (1 = the parse fails), *out_host_resolved (may be NULL) the number of entries the
+ * host finished.  to_type: INT32, UINT32, INT64, UINT64, FLOAT, DOUBLE or BOOL.  SSGPU_ERROR_NO_DEVICE on a bind-only context. */
+int ssgpu_dict_parse(ssgpu_ctx* ctx, const ssgpu_dict* d, int32_t to_type, void* out_values_host, uint8_t* out_failed_host, int64_t* out_host_resolved);
+
 /* Functions whose RESULT is a STRING (string_expressions.h:30-44,52-58; string_evaluators.h:41-67,96-132), as SSGPU_EXPR_OP:
  *   OPERATOR_LTRIM = 404, OPERATOR_RTRIM = 408, OPERATOR_TRIM = 412   strip byte 0x20 only ('\t', '\n' stay)
  *   OPERATOR_TOUPPER = 416                                           ascii_toupper: a-z only, bytes >= 0x80 and 0x00 untouched

@@ -481,6 +481,14 @@ inline const Expression* TrailingSubstring(const Expression* str, const Expressi
 inline const Expression* StringReplace(const Expression* haystack, const Expression* needle, const Expression* substitute) {
   return internal::Op(480, haystack, needle, substitute);
 }
+// PARSE_STRING (elementary_expressions.h:39-44): a STRING turned into `to_type`; the node's dtype is the target.  Quiet keeps the parser's
+// value where the parse fails, Nulling makes it NULL (ssgpu.h "PARSE_STRING")
+inline const Expression* ParseStringQuiet(DataType to_type, const Expression* const source) {
+  Expression* e = internal::Node(SSGPU_EXPR_OP, 437, to_type); e->args.emplace_back(source); return e;
+}
+inline const Expression* ParseStringNulling(DataType to_type, const Expression* const source) {
+  Expression* e = internal::Node(SSGPU_EXPR_OP, 438, to_type); e->args.emplace_back(source); return e;
+}
 // owning list of expressions (expression/base/expression.h): the arguments of Case / In
 class ExpressionList {
  public:

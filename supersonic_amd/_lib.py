@@ -145,6 +145,7 @@ SYMBOLS = [
     ("ssgpu_dict_decode", C.c_int, [P, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]),
     ("ssgpu_dict_extend", C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int64, C.POINTER(P), C.POINTER(C.c_int32)]),
     ("ssgpu_dict_eval", C.c_int, [P, P, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("ssgpu_dict_parse", C.c_int, [P, P, C.c_int32, P, C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
     ("ssgpu_plan_string_steps", C.c_int32, [P, C.POINTER(StringStep), C.c_int32]),
     ("ssgpu_dict_close", C.c_int, [P, P, C.POINTER(StringStep), C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]),
     ("ssgpu_dict_step_table", C.c_int, [P, C.c_int32, C.POINTER(C.c_int32)]),

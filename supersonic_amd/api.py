@@ -125,6 +125,20 @@ class StringDictionary(object):
                                            out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
+    def parse(self, to_type, context=None):
+        """ssgpu_dict_parse: every value parsed as `to_type` (INT32, UINT32, INT64, UINT64, FLOAT, DOUBLE or BOOL) on the device, the
+        reference's ParseString rules -> (values, failed, host_resolved): values[len(self)] of the type, failed bool[len(self)], and the
+        number of FLOAT / DOUBLE entries that left the device's exact fast path for the host's strtof / strtod."""
+        ctx = context or Context.default()
+        if to_type not in (INT32, UINT32, INT64, UINT64, FLOAT, DOUBLE, BOOL):
+            raise SupersonicException(L.ERROR_INVALID_ARGUMENT_VALUE, "StringDictionary.parse: a numeric type or BOOL")
+        values = np.zeros(max(len(self), 1), _NP[to_type])
+        failed = np.zeros(max(len(self), 1), np.uint8)
+        resolved = C.c_int64(0)
+        ctx.check(self.lib.ssgpu_dict_parse(ctx.handle, self.handle, int(to_type), values.ctypes.data_as(C.c_void_p),
+                                            failed.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(resolved)))
+        return values[:len(self)], failed[:len(self)] != 0, int(resolved.value)
+
     LTRIM, RTRIM, TRIM, TO_UPPER, TO_LOWER, SUBSTRING = 404, 408, 412, 416, 420, 427
     STRING_REPLACE = 480
 
@@ -758,6 +772,9 @@ def ToUpper(a): return _op(416, a)
 def Substring(s, pos, length): return _op(427, s, pos, length)
 def TrailingSubstring(s, pos): return _op(427, s, pos)
 def StringReplace(haystack, needle, substitute): return _op(480, haystack, needle, substitute)
+# PARSE_STRING (elementary_expressions.h:39-44): a STRING turned into `to_type`; Quiet keeps the parser's value where the parse fails, Nulling makes it NULL
+def ParseStringQuiet(to_type, e): return Expression(L.EXPR_OP, op=437, dtype=to_type, args=[e])
+def ParseStringNulling(to_type, e): return Expression(L.EXPR_OP, op=438, dtype=to_type, args=[e])
 
 
 class ExpressionList(object):

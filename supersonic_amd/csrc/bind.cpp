@@ -31,6 +31,7 @@ enum {
   OP_ACOSH = 844, OP_ATANH = 848,
   OP_SQRT_QUIET = 333, OP_SQRT_NULLING = 334, OP_SQRT_SIGNALING = 335, OP_CEIL = 342, OP_FLOOR = 346, OP_ABS = 360,
   OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_TOLOWER = 420, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476, OP_STRING_REPLACE = 480,
+  OP_PARSE_STRING_QUIET = 437, OP_PARSE_STRING_NULLING = 438,
   OP_CASE = 200, OP_IF = 204, OP_IN = 208, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265
 };
 
@@ -811,6 +812,24 @@ static Status bind_operator(const ssgpu_expr& x, std::vector<BExprP> args, int d
       // nothing folds here: a STRING constant is a code, and the dictionary arrives after the plan is made (ssgpu_plan_set_dict)
       BExprP e = make_op(op, SSGPU_INT32, hay->nullable || needle->nullable, "STRING_OFFSET(" + args[0]->name + ", " + args[1]->name + ")", {hay, needle}, depth);
       e->bits = fold ? 1 : 0;
+      *out = e;
+      return Status::OK();
+    }
+    case OP_PARSE_STRING_QUIET: case OP_PARSE_STRING_NULLING: {
+      // PARSE_STRING(child) to the node's dtype (elementary_expressions.h:39-44): a function of one STRING value again, so a table over
+      // the dictionary -- values and failure bytes, string_parse_kernels.hip -- gathered by the code.  Quiet: NULL iff the argument is, a
+      // failed parse yields the parser's value; Nulling: NULL where the argument is or the parse fails, so always nullable.
+      SS_RETURN_IF_ERROR(need(1));
+      if (args[0]->dtype != SSGPU_STRING)
+        return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string("PARSE_STRING needs a STRING argument, got ") + dtype_name(args[0]->dtype) + " in " + args[0]->name);
+      const int to = x.dtype;
+      if (to == SSGPU_STRING) { *out = args[0]; return Status::OK(); }   // the argument itself, under its own name (elementary_bound_expressions_test.cc:73,79)
+      if (to == SSGPU_DATE || to == SSGPU_DATETIME || to == SSGPU_BINARY)
+        return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, std::string("PARSE_STRING to ") + dtype_name(to) + " is not implemented (the numeric types and BOOL are): PARSE_STRING(" + args[0]->name + ")");
+      if (dtype_width(to) == 0 || !(dtype_is_numeric(to) || to == SSGPU_BOOL))
+        return Status::Error(SSGPU_ERROR_INVALID_ARGUMENT_VALUE, "PARSE_STRING: unknown target type " + std::to_string(to));
+      BExprP e = make_op(op, to, args[0]->nullable || op == OP_PARSE_STRING_NULLING, "PARSE_STRING(" + args[0]->name + ")", {args[0]}, depth);
+      e->str_null = args[0]->kind == BExpr::NULLCONST;   // an all-NULL result: no table
       *out = e;
       return Status::OK();
     }

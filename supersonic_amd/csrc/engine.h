@@ -118,12 +118,17 @@ struct JoinSpec {
 // 476 STRING_OFFSET of the value whose code is `needle_code`, compared through ascii_tolower when `fold`; or the table of a
 // string-producing function (is_string_producer(fn): 404 / 408 / 412 / 416 / 427 with SUBSTRING's pos / len / has_len, 480
 // STRING_REPLACE with pos = the needle's code and len = the substitute's, has_len false), table[c] = the
-// code of fn(value c) in the plan's CLOSED dictionary, which holds it (ssgpu_dict_close; runtime.cpp only uploads it)
+// code of fn(value c) in the plan's CLOSED dictionary, which holds it (ssgpu_dict_close; runtime.cpp only uploads it); or --
+// fn == DICT_FN_PARSE -- the PARSE_STRING tables of target type `to_type` (string_parse_kernels.hip): the slot's data is value c parsed,
+// 1 / 4 / 8 bytes an entry, and its is_null the byte "the parse of value c failed".  ParseStringQuiet 437 and ParseStringNulling
+// 438 of one target type share the slot: the tables are the same, Nulling reads both and Quiet the values alone.
 struct JoinGather {
   int join_id; int rhs_col; bool is_null_mask; int fn = 0; int32_t needle_code = 0; bool fold = false;
   int64_t pos = 0, len = 0; bool has_len = false;
+  int to_type = 0;
 };
 enum { JOIN_GATHER_DICT_TABLE = -2 };
+enum { DICT_FN_PARSE = 437 };
 inline bool is_string_producer(int fn) { return fn == 404 || fn == 408 || fn == 412 || fn == 416 || fn == 427 || fn == 480; }
 enum { JOIN_GATHER_RUN_START = -1, JOIN_GATHER_RUN_COUNT = -2 };   // rhs_col of a multi join's per-key run arrays
 

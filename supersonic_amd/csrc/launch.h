@@ -339,6 +339,12 @@ hipError_t ssgpu_launch_str_recode(const int32_t* src, const uint8_t* nulls, con
 #define STRFN_HEAP_PAD 32
 hipError_t ssgpu_launch_str_fn(const uint8_t* heap, const uint64_t* offs, uint64_t n, int fn, const uint8_t* needle, uint32_t needle_len,
                                int fold, uint32_t* table, hipStream_t s);
+// PARSE_STRING of the dictionary's values (string_parse_kernels.hip): values[c] = value c parsed as `to_type` (an SSGPU_* type of 1, 4
+// or 8 bytes: BOOL, INT32 / UINT32 / FLOAT, INT64 / UINT64 / DOUBLE), failed[c] = 0 parsed, 1 failed, or -- FLOAT / DOUBLE only --
+// STRPARSE_HARD: outside the device's exact fast path, values[c] is 0 and the host decides with strtof / strtod.  Same heap contract.
+#define STRPARSE_HARD 2
+#define STRPARSE_WINDOW 64   /* FLOAT / DOUBLE: bytes one lane walks, from the first byte behind the sign that is not '0' to the value's trimmed end */
+hipError_t ssgpu_launch_str_parse(const uint8_t* heap, const uint64_t* offs, uint64_t n, int to_type, void* values, uint8_t* failed, hipStream_t s);
 // string-producing functions of the dictionary's values (string_map_kernels.hip), one closing step of ssgpu_dict_close: the length
 // pass fills lens[0, n) with the values' own lengths, lens[n, 2n) with their images' and src[i] with the image's first byte in `heap`
 // (fn: 404 LTRIM, 408 RTRIM, 412 TRIM, 416 TO_UPPER, 420 TO_LOWER, 427 SUBSTRING(pos, len) -- to the end without has_len); the write

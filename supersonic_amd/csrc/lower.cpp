@@ -35,7 +35,7 @@ enum {
   OP_BITWISE_NOT = 68, OP_BITWISE_XOR = 72, OP_SHIFT_LEFT = 76, OP_SHIFT_RIGHT = 80,
   OP_BITWISE_ANDNOT = 84, OP_EQUAL = 100, OP_NOT_EQUAL = 104, OP_LESS = 116, OP_LESS_OR_EQUAL = 120,
   OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265, OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476,
-  OP_STRING_REPLACE = 480
+  OP_STRING_REPLACE = 480, OP_PARSE_STRING_QUIET = 437, OP_PARSE_STRING_NULLING = 438
 };
 
 // machine type classes
@@ -157,6 +157,17 @@ class Emitter {
       if (t.join_id == JOIN_GATHER_DICT_TABLE && t.fn == fn && t.pos == pos && t.len == len && t.has_len == has_len) return (int)i;
     }
     JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.fn = fn; g.pos = pos; g.len = len; g.has_len = has_len;
+    P->gathers.push_back(g);
+    return (int)P->gathers.size() - 1;
+  }
+  // ... and the PARSE_STRING tables of a target type (values + failure bytes, string_parse_kernels.hip): ONE slot per type, whichever
+  // of ParseStringQuiet / ParseStringNulling asks
+  int parse_slot(int to_type) {
+    for (size_t i = 0; i < P->gathers.size(); ++i) {
+      const JoinGather& t = P->gathers[i];
+      if (t.join_id == JOIN_GATHER_DICT_TABLE && t.fn == DICT_FN_PARSE && t.to_type == to_type) return (int)i;
+    }
+    JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.fn = DICT_FN_PARSE; g.to_type = to_type;
     P->gathers.push_back(g);
     return (int)P->gathers.size() - 1;
   }
@@ -601,6 +612,22 @@ Status Emitter::value(const BExprP& e, Val* out) {
           v.reg = new_reg(4);
           LInstr& i = emit(VM_GATHER_32); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot;
           v.null = a[0].null;
+        } break;
+        case OP_PARSE_STRING_QUIET: case OP_PARSE_STRING_NULLING: {
+          // parse(s) = V[code(s)], "it failed" = F[code(s)]: both tables sit in ONE slot -- V as its data, F as its is_null -- so Nulling is
+          // GATHER_NULL on the slot the value came from, ORed with the argument's own NULLs, and Quiet never reads F.  A code is never
+          // VM_NONE (NULL rows and the rows past the last tile carry code 0; both tables have an entry 0), so GATHER_NULL says F and nothing else.
+          if (e->str_null) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // PARSE_STRING(NULL)
+          const int code = materialize(a[0]);
+          const int slot = parse_slot(e->dtype);
+          v.reg = new_reg(v.width);
+          { LInstr& i = emit(v.width == 8 ? VM_GATHER_64 : v.width == 4 ? VM_GATHER_32 : VM_GATHER_8); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot; }
+          v.null = a[0].null;
+          if (e->op == OP_PARSE_STRING_NULLING) {
+            const int failed = new_reg(1);
+            { LInstr& i = emit(VM_GATHER_NULL); i.dst = failed; i.a = code; i.imm = (uint64_t)slot; }
+            v.null = or_null(a[0].null, failed);
+          }
         } break;
         case OP_NEGATE: v.reg = unop(pick(mt, VM_NEG_I32, VM_NEG_I32, VM_NEG_I64, VM_NEG_I64, VM_NEG_F32, VM_NEG_F64), a[0], v.width); v.null = a[0].null; break;
         case OP_BITWISE_AND: v.reg = binop(v.width == 4 ? VM_BAND_32 : VM_BAND_64, a[0], a[1], v.width); v.null = or_null(a[0].null, a[1].null); break;

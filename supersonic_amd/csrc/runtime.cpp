@@ -13,6 +13,8 @@
 #include <set>
 #include <mutex>
 #include <stdio.h>
+#include <stdlib.h>
+#include <locale.h>
 #include <string.h>
 #include <algorithm>
 #include <cmath>
@@ -404,9 +406,13 @@ struct ssgpu_plan {
   struct DictTables {
     bool built = false; uint64_t built_gen = 0; const ssgpu_dict* built_for = nullptr;
     DictDevice dev; DevBuf needle;
-    typedef std::tuple<int, int32_t, bool, int64_t, int64_t, bool> Key;   // function, needle code, fold; a producer's position, length, has_len
-    static Key key(const JoinGather& g) { return Key(g.fn, g.needle_code, g.fold, g.pos, g.len, g.has_len); }
+    typedef std::tuple<int, int32_t, bool, int64_t, int64_t, bool, int> Key;   // function, needle code, fold; a producer's position, length, has_len; PARSE_STRING's target type
+    static Key key(const JoinGather& g) { return Key(g.fn, g.needle_code, g.fold, g.pos, g.len, g.has_len, g.to_type); }
     std::map<Key, DevBuf> tables;
+    // PARSE_STRING (fn DICT_FN_PARSE, string_parse_kernels.hip): `tables` holds the values, this the failure bytes the slot's is_null points
+    // at; host_resolved: the FLOAT / DOUBLE entries the device left to the host's strtof / strtod when the tables were last built
+    std::map<Key, DevBuf> failed;
+    int64_t host_resolved = 0;
   } dict_tables;
   std::vector<ssgpu_column> last_cols; int64_t last_base = 0; bool last_partial = false;   // the last run's input (a deferred overflow repeats it)
   // ssgpu_plan_run_host: two alternating sets of device columns the host rows are staged through, and the chunks' partial states
@@ -1127,6 +1133,12 @@ const char* ssgpu_plan_describe(ssgpu_plan* p) {
           lines += " (codes of the closed dictionary)\n";
           continue;
         }
+        if (g.fn == DICT_FN_PARSE) {
+          lines += std::string("dictionary table: PARSE_STRING to ") + dtype_name(g.to_type) + " (values and failure bytes)";
+          if (p->dict_tables.built && dtype_is_float(g.to_type)) lines += " host-resolved entries of the plan's floating tables: " + std::to_string(p->dict_tables.host_resolved);
+          lines += "\n";
+          continue;
+        }
         if (g.fn != 476) { lines += "dictionary table: LENGTH\n"; continue; }
         const char* bytes = nullptr; int32_t len = 0;
         lines += "dictionary table: STRING_OFFSET needle code " + std::to_string(g.needle_code) +
@@ -1347,6 +1359,52 @@ int dict_table_build(ssgpu_ctx* c, const DictDevice& D, int fn, const char* need
                                  fold ? 1 : 0, table->as<uint32_t>(), c->stream));
   return SSGPU_OK;
 }
+// PARSE_STRING: values[c] = value c parsed as `to_type`, failed[c] = 1 where that parse fails (string_parse_kernels.hip).  The device decides
+// the integer and BOOL targets alone.  Of a FLOAT / DOUBLE table it fills what lies on its exact fast path and marks the rest
+// STRPARSE_HARD; those entries are finished here with the reference's own parser -- glibc strtof / strtod in the C locale on the value's
+// bytes cut at the first 0x00, the value kept whatever the outcome (safe_strtof / safe_strtod, numbers.cc:802-829) -- and both tables
+// patched before anything reads them.  *host_resolved += the number of such entries.  An empty dictionary gets one entry, 0 / not failed.
+static locale_t parse_c_locale() { static locale_t loc = newlocale(LC_ALL_MASK, "C", (locale_t)0); return loc; }
+int dict_parse_build(ssgpu_ctx* c, const DictDevice& D, const ssgpu_dict* d, int to_type, DevBuf* values, DevBuf* failed, int64_t* host_resolved,
+                     hipEvent_t after_kernel = nullptr /* recorded behind the kernel, in front of the host's share */) {
+  const size_t w = (size_t)dtype_width(to_type), n = (size_t)D.n;
+  HIP_TRY(c, values->ensure(std::max<size_t>(n, 1) * w));
+  HIP_TRY(c, failed->ensure(std::max<size_t>(n, 1)));
+  if (n == 0) {
+    HIP_TRY(c, hipMemsetAsync(values->p, 0, w, c->stream)); HIP_TRY(c, hipMemsetAsync(failed->p, 0, 1, c->stream));
+    if (after_kernel) HIP_TRY(c, hipEventRecord(after_kernel, c->stream));
+    return SSGPU_OK;
+  }
+  HIP_TRY(c, ssgpu_launch_str_parse(D.heap.as<const uint8_t>(), D.offs.as<const uint64_t>(), D.n, to_type, values->p, failed->as<uint8_t>(), c->stream));
+  if (after_kernel) HIP_TRY(c, hipEventRecord(after_kernel, c->stream));
+  if (!dtype_is_float(to_type)) return SSGPU_OK;
+  std::vector<uint8_t> f(n);
+  HIP_TRY(c, hipMemcpyAsync(f.data(), failed->p, n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<size_t> hard;
+  for (size_t i = 0; i < n; ++i) if (f[i] == STRPARSE_HARD) hard.push_back(i);
+  if (hard.empty()) return SSGPU_OK;
+  std::vector<char> v(n * w);
+  HIP_TRY(c, hipMemcpyAsync(v.data(), values->p, n * w, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::string text;
+  for (size_t i : hard) {
+    const char* bytes = nullptr; int32_t len = 0;
+    if (ssgpu_dict_decode(d, (int32_t)i, &bytes, &len) != SSGPU_OK) { c->err = "PARSE_STRING: the dictionary lost a value"; return SSGPU_ERROR_UNKNOWN; }
+    text.assign(bytes, (size_t)len);
+    const char* str = text.c_str();   // (cut at the first 0x00 by whoever reads it as a C string)
+    char* end = nullptr;
+    if (to_type == SSGPU_FLOAT) { const float x = strtof_l(str, &end, parse_c_locale()); memcpy(v.data() + i * w, &x, w); }
+    else { const double x = strtod_l(str, &end, parse_c_locale()); memcpy(v.data() + i * w, &x, w); }
+    if (end != str) while (*end == ' ' || (unsigned)(*end - 9) < 5u) ++end;   // ascii_isspace
+    f[i] = (*str != '\0' && *end == '\0') ? 0 : 1;
+  }
+  HIP_TRY(c, hipMemcpyAsync(values->p, v.data(), n * w, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(failed->p, f.data(), n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host copies go out of scope)
+  *host_resolved += (int64_t)hard.size();
+  return SSGPU_OK;
+}
 // the plan's step list (ssgpu_plan_string_steps): the string-producing nodes of every program of every stage, in the order they are evaluated
 static void plan_string_steps(const ssgpu_plan* p, std::vector<ssgpu_string_step>* out) {
   for (auto& st : p->stages)
@@ -1370,7 +1428,12 @@ int ensure_dict_tables(ssgpu_plan* p) {
   if (!p->dict) {
     std::vector<ssgpu_string_step> producers;
     plan_string_steps(p, &producers);
-    c->err = producers.empty() ? "LENGTH / STRING_OFFSET of a STRING value need the plan's dictionary (ssgpu_plan_set_dict)"
+    bool parses = false, others = false;
+    for (auto& st : p->stages)
+      for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
+        for (auto& g : pr->gathers) if (g.join_id == JOIN_GATHER_DICT_TABLE) (g.fn == DICT_FN_PARSE ? parses : others) = true;
+    if (parses && !others && producers.empty()) { c->err = "PARSE_STRING of a STRING value needs the plan's dictionary (ssgpu_plan_set_dict)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+    c->err = producers.empty() ? "LENGTH / STRING_OFFSET / PARSE_STRING of a STRING value need the plan's dictionary (ssgpu_plan_set_dict)"
                                : "LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING / STRING_REPLACE need the plan's dictionary, closed under the plan's steps (ssgpu_plan_string_steps, "
                                  "ssgpu_dict_close, ssgpu_plan_set_dict)";
     return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
@@ -1396,13 +1459,15 @@ int ensure_dict_tables(ssgpu_plan* p) {
       ++k;
     } }
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // (an earlier run may still read the tables that are replaced now)
-  bool computed = false;   // some table is COMPUTED from the packed dictionary (LENGTH / STRING_OFFSET)
+  T.host_resolved = 0;
+  bool computed = false;   // some table is COMPUTED from the packed dictionary (LENGTH / STRING_OFFSET / PARSE_STRING)
   for (auto& st : p->stages)
     for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
       for (auto& g : pr->gathers) computed = computed || (g.join_id == JOIN_GATHER_DICT_TABLE && !is_string_producer(g.fn));
   int rc = computed ? dict_upload(c, p->dict, &T.dev) : SSGPU_OK;
   if (rc != SSGPU_OK) return rc;
   const int32_t n = ssgpu_dict_size(p->dict);
+  std::set<ssgpu_plan::DictTables::Key> parse_built;
   for (auto& st : p->stages)
     for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
       for (auto& g : pr->gathers) {
@@ -1417,6 +1482,14 @@ int ensure_dict_tables(ssgpu_plan* p) {
           HIP_TRY(c, table.ensure((size_t)std::max<int32_t>(n, 1) * 4));
           if (n) HIP_TRY(c, hipMemcpyAsync(table.p, ssgpu_dict_step_table_data(p->dict, k), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
           else HIP_TRY(c, hipMemsetAsync(table.p, 0, 4, c->stream));
+          continue;
+        }
+        if (g.fn == DICT_FN_PARSE) {   // the same (target type) slot in several programs: built once
+          const ssgpu_plan::DictTables::Key key = ssgpu_plan::DictTables::key(g);
+          if (!parse_built.insert(key).second) continue;
+          rc = dict_parse_build(c, T.dev, p->dict, g.to_type, &T.tables[key], &T.failed[key], &T.host_resolved);
+          if (rc != SSGPU_OK) return rc;
+          p->counters.n_launches += 1;
           continue;
         }
         const char* needle = ""; int32_t nlen = 0;
@@ -1440,6 +1513,10 @@ void apply_joins(const ssgpu_plan* p, const StageExec& ex, const Program& prog, 
     if (jg.join_id == JOIN_GATHER_DICT_TABLE) {   // a table over the STRING dictionary, indexed by a code (ensure_dict_tables)
       auto it = p->dict_tables.tables.find(ssgpu_plan::DictTables::key(jg));
       P->join_cols[g].data = it != p->dict_tables.tables.end() ? it->second.p : nullptr; P->join_cols[g].is_null = nullptr;
+      if (jg.fn == DICT_FN_PARSE) {   // PARSE_STRING: the slot's NULL mask is the failure table (GATHER_NULL of ParseStringNulling)
+        auto f = p->dict_tables.failed.find(ssgpu_plan::DictTables::key(jg));
+        if (f != p->dict_tables.failed.end()) P->join_cols[g].is_null = f->second.as<const uint8_t>();
+      }
       continue;
     }
     if (jg.rhs_col < 0) {   // the per-key run arrays of a NOT_UNIQUE join, indexed by the probed slot
@@ -4593,6 +4670,45 @@ int ssgpu_dict_eval(ssgpu_ctx* c, const ssgpu_dict* d, int32_t fn, const char* n
     float up = 0, k = 0;
     (void)hipEventElapsedTime(&up, ev[0], ev[1]); (void)hipEventElapsedTime(&k, ev[1], ev[2]);
     fprintf(stderr, "[ssgpu dict_eval] values %d upload_ms %.4f kernel_ms %.4f\n", n, up, k);
+  }
+  return SSGPU_OK;
+}
+// The PARSE_STRING tables of `d` without a plan (string_parse_kernels.hip + the host's strtof / strtod for what the device leaves):
+// out_values_host: ssgpu_dict_size(d) entries of to_type's width, out_failed_host: one byte per value, *out_host_resolved: how many
+// entries the host finished.
+int ssgpu_dict_parse(ssgpu_ctx* c, const ssgpu_dict* d, int32_t to_type, void* out_values_host, uint8_t* out_failed_host, int64_t* out_host_resolved) {
+  if (!c) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  if (!d || !(dtype_is_numeric(to_type) || to_type == SSGPU_BOOL)) {
+    c->err = "ssgpu_dict_parse: a dictionary and a target type of INT32, UINT32, INT64, UINT64, FLOAT, DOUBLE or BOOL";
+    return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
+  }
+  if (c->device < 0) { c->err = "no gfx950 device bound to this context (bind-only context)"; return SSGPU_ERROR_NO_DEVICE; }
+  const int32_t n = ssgpu_dict_size(d);
+  if (n > 0 && (!out_values_host || !out_failed_host)) { c->err = "ssgpu_dict_parse: no result buffer"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  DictDevice D; DevBuf values, failed;
+  struct Events { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } events;
+  hipEvent_t* ev = events.e;
+  const bool timed = c->debug_timing != 0;   // development: upload, kernel and host-share times on stderr (tools/string_parse_bench.py)
+  if (timed) { for (int i = 0; i < 4; ++i) HIP_TRY(c, hipEventCreate(&ev[i])); HIP_TRY(c, hipEventRecord(ev[0], c->stream)); }
+  int rc = dict_upload(c, d, &D);
+  if (rc != SSGPU_OK) return rc;
+  if (timed) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+  int64_t resolved = 0;
+  rc = dict_parse_build(c, D, d, to_type, &values, &failed, &resolved, timed ? ev[3] : nullptr);
+  if (rc != SSGPU_OK) return rc;
+  if (timed) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
+  if (n > 0) {
+    HIP_TRY(c, hipMemcpyAsync(out_values_host, values.p, (size_t)n * (size_t)dtype_width(to_type), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_failed_host, failed.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (out_host_resolved) *out_host_resolved = resolved;
+  if (timed) {
+    float up = 0, k = 0, h = 0;
+    (void)hipEventElapsedTime(&up, ev[0], ev[1]); (void)hipEventElapsedTime(&k, ev[1], ev[3]); (void)hipEventElapsedTime(&h, ev[3], ev[2]);
+    // host_ms: a floating target's read-back of the failure bytes, the host's strtof / strtod and the patched tables' way back
+    fprintf(stderr, "[ssgpu dict_parse] values %d upload_ms %.4f kernel_ms %.4f host_ms %.4f host_resolved %lld\n", n, up, k, h, (long long)resolved);
   }
   return SSGPU_OK;
 }
