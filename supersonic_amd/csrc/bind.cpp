@@ -15,26 +15,6 @@
 
 namespace ssgpu {
 
-// OperatorId values used here (supersonic/expression/proto/operators.proto)
-enum {
-  OP_ADD = 0, OP_MULTIPLY = 4, OP_SUBTRACT = 8, OP_DIVIDE_QUIET = 13, OP_DIVIDE_NULLING = 14,
-  OP_DIVIDE_SIGNALING = 15, OP_CPP_DIVIDE_NULLING = 18, OP_CPP_DIVIDE_SIGNALING = 19,
-  OP_MODULUS_NULLING = 26, OP_MODULUS_SIGNALING = 27, OP_NEGATE = 36, OP_AND = 40, OP_OR = 44,
-  OP_AND_NOT = 48, OP_NOT = 52, OP_XOR = 56, OP_BITWISE_AND = 60, OP_BITWISE_OR = 64,
-  OP_BITWISE_NOT = 68, OP_BITWISE_XOR = 72, OP_SHIFT_LEFT = 76, OP_SHIFT_RIGHT = 80,
-  OP_BITWISE_ANDNOT = 84, OP_EQUAL = 100, OP_NOT_EQUAL = 104, OP_LESS = 116, OP_LESS_OR_EQUAL = 120,
-  OP_IS_ODD = 140, OP_IS_EVEN = 144, OP_IS_FINITE = 148, OP_IS_INF = 152, OP_IS_NAN = 156, OP_IS_NORMAL = 160,
-  OP_ROUND = 300, OP_TRUNC = 304, OP_CEIL_TO_INT = 308, OP_FLOOR_TO_INT = 312, OP_ROUND_TO_INT = 316,
-  OP_ROUND_WITH_MULTIPLIER = 364, OP_EXP = 320, OP_LN_QUIET = 325, OP_LN_NULLING = 326, OP_LOG10_QUIET = 329, OP_LOG10_NULLING = 330, OP_POW_QUIET = 353,
-  OP_POW_NULLING = 354, OP_POW_SIGNALING = 355, OP_LOG2_QUIET = 357, OP_LOG2_NULLING = 358, OP_SIN = 800, OP_COS = 804, OP_TAN = 808,
-  OP_ASIN = 812, OP_ACOS = 816, OP_ATAN = 820, OP_ATAN2 = 824, OP_SINH = 828, OP_COSH = 832, OP_TANH = 836, OP_ASINH = 840,
-  OP_ACOSH = 844, OP_ATANH = 848,
-  OP_SQRT_QUIET = 333, OP_SQRT_NULLING = 334, OP_SQRT_SIGNALING = 335, OP_CEIL = 342, OP_FLOOR = 346, OP_ABS = 360,
-  OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_TOLOWER = 420, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476, OP_STRING_REPLACE = 480,
-  OP_PARSE_STRING_QUIET = 437, OP_PARSE_STRING_NULLING = 438,
-  OP_CASE = 200, OP_IF = 204, OP_IN = 208, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265
-};
-
 const char* dtype_name(int t) {
   switch (t) {
     case SSGPU_INT32: return "INT32"; case SSGPU_INT64: return "INT64"; case SSGPU_UINT32: return "UINT32";
@@ -730,7 +710,7 @@ static Status bind_operator(const ssgpu_expr& x, std::vector<BExprP> args, int d
     // ---- functions whose result is a STRING: a code of the plan's CLOSED dictionary, gathered from a table the dictionary brings
     // along (ssgpu.h "THE CLOSED DICTIONARY"; lower.cpp).  Names and refusals: string_expressions_test.cc:37-87.
     case OP_LTRIM: case OP_RTRIM: case OP_TRIM: case OP_TOUPPER: {
-      const char* nm = op == OP_LTRIM ? "LTRIM" : op == OP_RTRIM ? "RTRIM" : op == OP_TRIM ? "TRIM" : "TO_UPPER";
+      const char* nm = string_fn_name(op);
       SS_RETURN_IF_ERROR(need(1));
       if (args[0]->dtype != SSGPU_STRING)
         return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH, std::string(nm) + " needs a STRING argument, got " + dtype_name(args[0]->dtype) + " in " + args[0]->name);

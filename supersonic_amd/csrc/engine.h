@@ -11,11 +11,13 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/ssgpu.h"
 #include "vm.h"
 #include "launch.h"
+#include "opids.h"
 
 // seams.cpp: a dictionary over values already sorted and unique (`offsets[n + 1]` into `heap`), taken without sorting again --
 // how the distinct strings a device block's STRING columns were encoded with come back to the host
@@ -68,9 +70,9 @@ struct BExpr {
   int join_id = -1;    // JOINCOL / JOINMATCH / JOINSTART / JOINCNT: index into the stage's joins
   uint64_t bits = 0;   // CONST: raw value bits in the column's device width
   int filter_depth = 0;  // number of Filter operations below this expression
-  // string-producing OP (LTRIM 404 ... SUBSTRING 427; args = the STRING argument alone): SUBSTRING's constant position and length
+  // string-producing OP (OP_LTRIM ... OP_SUBSTRING; args = the STRING argument alone): SUBSTRING's constant position and length
   // (str_has_len: the 3-argument form); str_null: a NULL position / length -- the result is NULL everywhere and needs no table.
-  // STRING_REPLACE 480 keeps its constant needle's code in str_pos and its substitute's in str_len (str_null: one of them is NULL)
+  // OP_STRING_REPLACE keeps its constant needle's code in str_pos and its substitute's in str_len (str_null: one of them is NULL)
   int64_t str_pos = 0, str_len = 0;
   bool str_has_len = false, str_null = false;
   std::vector<BExprP> args;
@@ -113,23 +115,73 @@ struct JoinSpec {
   bool wide = false;                     // the packed key takes two 64-bit words (JOIN_PROBE_WIDE)
   int depth = 0;                         // number of Filters below the join: rows their selection dropped are not probed
 };
-// slot i of VmParams.join_cols: a column (or NULL mask) of a join's rhs table, or -- join_id == JOIN_GATHER_DICT_TABLE -- a table
-// over the plan's STRING dictionary, indexed by a code: table[c] = fn(value c) (string_fn_kernels.hip), fn = 400 LENGTH,
-// 476 STRING_OFFSET of the value whose code is `needle_code`, compared through ascii_tolower when `fold`; or the table of a
-// string-producing function (is_string_producer(fn): 404 / 408 / 412 / 416 / 427 with SUBSTRING's pos / len / has_len, 480
-// STRING_REPLACE with pos = the needle's code and len = the substitute's, has_len false), table[c] = the
-// code of fn(value c) in the plan's CLOSED dictionary, which holds it (ssgpu_dict_close; runtime.cpp only uploads it); or --
-// fn == DICT_FN_PARSE -- the PARSE_STRING tables of target type `to_type` (string_parse_kernels.hip): the slot's data is value c parsed,
-// 1 / 4 / 8 bytes an entry, and its is_null the byte "the parse of value c failed".  ParseStringQuiet 437 and ParseStringNulling
-// 438 of one target type share the slot: the tables are the same, Nulling reads both and Quiet the values alone.
+// A table over the plan's STRING dictionary, indexed by a code: what it holds.  Three kinds, told apart by the function:
+//  - computed (string_fn_kernels.hip): table[c] = fn(value c), fn = OP_LENGTH, or OP_STRING_OFFSET of the value whose code is
+//    `needle_code`, compared through ascii_tolower when `fold`;
+//  - producer (is_string_producer(fn): OP_LTRIM / OP_RTRIM / OP_TRIM / OP_TOUPPER, OP_SUBSTRING with pos / len / has_len, OP_STRING_REPLACE
+//    with pos = the needle's code and len = the substitute's, has_len false): table[c] = the code of fn(value c) in the plan's CLOSED
+//    dictionary, which holds it (ssgpu_dict_close; string_dict.cpp only uploads it);
+//  - parse (fn == DICT_FN_PARSE, string_parse_kernels.hip): the PARSE_STRING tables of target type `to_type` -- value c parsed, 1 / 4 / 8
+//    bytes an entry, and the byte "the parse of value c failed".  OP_PARSE_STRING_QUIET and OP_PARSE_STRING_NULLING of one target type
+//    share the tables: Nulling reads both and Quiet the values alone.
+// Two nodes share a table exactly when their specs are equal.  Each kind's maker sets its own parameters and leaves the others at
+// their defaults, so equality of whole specs is equality of the kind's own parameters (what lower.cpp's three slot finders compared).
+enum { DICT_FN_PARSE = OP_PARSE_STRING_QUIET };
+inline bool is_string_producer(int fn) {
+  return fn == OP_LTRIM || fn == OP_RTRIM || fn == OP_TRIM || fn == OP_TOUPPER || fn == OP_SUBSTRING || fn == OP_STRING_REPLACE;
+}
+// the display name of a string function (bound expression names, describe lines)
+inline const char* string_fn_name(int fn) {
+  switch (fn) {
+    case OP_LENGTH: return "LENGTH"; case OP_LTRIM: return "LTRIM"; case OP_RTRIM: return "RTRIM"; case OP_TRIM: return "TRIM";
+    case OP_TOUPPER: return "TO_UPPER"; case OP_TOLOWER: return "TO_LOWER"; case OP_SUBSTRING: return "SUBSTRING";
+    case OP_STRING_OFFSET: return "STRING_OFFSET"; case OP_STRING_REPLACE: return "STRING_REPLACE";
+    case OP_PARSE_STRING_QUIET: case OP_PARSE_STRING_NULLING: return "PARSE_STRING";
+  }
+  return "?";
+}
+struct DictTableSpec {
+  enum Kind { COMPUTED, PRODUCER, PARSE };
+  int fn = 0;
+  int32_t needle_code = 0; bool fold = false;          // computed
+  int64_t pos = 0, len = 0; bool has_len = false;      // producer
+  int to_type = 0;                                     // parse
+  Kind kind() const { return fn == DICT_FN_PARSE ? PARSE : is_string_producer(fn) ? PRODUCER : COMPUTED; }
+  static DictTableSpec computed(int fn, int32_t needle_code, bool fold) {
+    DictTableSpec s; s.fn = fn;
+    if (fn == OP_STRING_OFFSET) { s.needle_code = needle_code; s.fold = fold; }
+    return s;
+  }
+  // SUBSTRING's length counts only in the 3-argument form (same_step ignores it otherwise); the trims and TO_UPPER have no parameters
+  static DictTableSpec producer(int fn, int64_t pos, int64_t len, bool has_len) {
+    DictTableSpec s; s.fn = fn;
+    if (fn == OP_STRING_REPLACE) { s.pos = pos; s.len = len; }
+    if (fn == OP_SUBSTRING) { s.pos = pos; s.has_len = has_len; s.len = has_len ? len : 0; }
+    return s;
+  }
+  static DictTableSpec parse(int to_type) { DictTableSpec s; s.fn = DICT_FN_PARSE; s.to_type = to_type; return s; }
+  // a producer's step, as the plan's step list and the closed dictionary state it
+  ssgpu_string_step step() const { ssgpu_string_step st; st.fn = fn; st.has_len = has_len ? 1 : 0; st.pos = pos; st.len = len; return st; }
+  bool operator==(const DictTableSpec& o) const {
+    return fn == o.fn && needle_code == o.needle_code && fold == o.fold && pos == o.pos && len == o.len && has_len == o.has_len && to_type == o.to_type;
+  }
+  bool operator<(const DictTableSpec& o) const {
+    return std::tie(fn, needle_code, fold, pos, len, has_len, to_type) < std::tie(o.fn, o.needle_code, o.fold, o.pos, o.len, o.has_len, o.to_type);
+  }
+};
+// "this plan step is that dictionary step": STRING_REPLACE's pos / len are codes of the same dictionary; SUBSTRING's len is ignored without has_len
+inline bool same_step(const ssgpu_string_step& a, const ssgpu_string_step& b) {
+  if (a.fn == OP_STRING_REPLACE) return b.fn == OP_STRING_REPLACE && a.pos == b.pos && a.len == b.len;
+  return a.fn == b.fn && (a.fn != OP_SUBSTRING || (a.pos == b.pos && (a.has_len != 0) == (b.has_len != 0) && (!a.has_len || a.len == b.len)));
+}
+inline bool same_step(const ssgpu_string_step& a, const DictTableSpec& producer) { return same_step(a, producer.step()); }
+// slot i of VmParams.join_cols: a column (or NULL mask) of a join's rhs table, or -- join_id == JOIN_GATHER_DICT_TABLE -- the table
+// `table` over the plan's STRING dictionary (a parse table's slot: its data the values, its is_null the failure bytes)
 struct JoinGather {
-  int join_id; int rhs_col; bool is_null_mask; int fn = 0; int32_t needle_code = 0; bool fold = false;
-  int64_t pos = 0, len = 0; bool has_len = false;
-  int to_type = 0;
+  int join_id; int rhs_col; bool is_null_mask;
+  DictTableSpec table;
 };
 enum { JOIN_GATHER_DICT_TABLE = -2 };
-enum { DICT_FN_PARSE = 437 };
-inline bool is_string_producer(int fn) { return fn == 404 || fn == 408 || fn == 412 || fn == 416 || fn == 427 || fn == 480; }
 enum { JOIN_GATHER_RUN_START = -1, JOIN_GATHER_RUN_COUNT = -2 };   // rhs_col of a multi join's per-key run arrays
 
 // Lowered instruction over virtual registers.  A register is an LDS array of

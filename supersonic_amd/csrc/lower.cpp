@@ -20,24 +20,6 @@
 
 namespace ssgpu {
 
-enum {
-  OP_ADD = 0, OP_MULTIPLY = 4, OP_SUBTRACT = 8, OP_DIVIDE_QUIET = 13, OP_DIVIDE_NULLING = 14,
-  OP_DIVIDE_SIGNALING = 15, OP_CPP_DIVIDE_NULLING = 18, OP_CPP_DIVIDE_SIGNALING = 19,
-  OP_MODULUS_NULLING = 26, OP_MODULUS_SIGNALING = 27, OP_NEGATE = 36,
-  OP_IS_ODD = 140, OP_IS_EVEN = 144, OP_IS_FINITE = 148, OP_IS_INF = 152, OP_IS_NAN = 156, OP_IS_NORMAL = 160,
-  OP_ROUND_WITH_MULTIPLIER = 364, OP_EXP = 320, OP_LN_QUIET = 325, OP_LN_NULLING = 326, OP_LOG10_QUIET = 329, OP_LOG10_NULLING = 330, OP_POW_QUIET = 353,
-  OP_POW_NULLING = 354, OP_POW_SIGNALING = 355, OP_LOG2_QUIET = 357, OP_LOG2_NULLING = 358, OP_SIN = 800, OP_COS = 804, OP_TAN = 808,
-  OP_ASIN = 812, OP_ACOS = 816, OP_ATAN = 820, OP_ATAN2 = 824, OP_SINH = 828, OP_COSH = 832, OP_TANH = 836, OP_ASINH = 840,
-  OP_ACOSH = 844, OP_ATANH = 848,
-  OP_ROUND = 300, OP_TRUNC = 304, OP_CEIL_TO_INT = 308, OP_FLOOR_TO_INT = 312, OP_SQRT_QUIET = 333, OP_SQRT_NULLING = 334,
-  OP_SQRT_SIGNALING = 335, OP_CEIL = 342, OP_FLOOR = 346, OP_ABS = 360, OP_AND = 40, OP_OR = 44,
-  OP_AND_NOT = 48, OP_NOT = 52, OP_XOR = 56, OP_BITWISE_AND = 60, OP_BITWISE_OR = 64,
-  OP_BITWISE_NOT = 68, OP_BITWISE_XOR = 72, OP_SHIFT_LEFT = 76, OP_SHIFT_RIGHT = 80,
-  OP_BITWISE_ANDNOT = 84, OP_EQUAL = 100, OP_NOT_EQUAL = 104, OP_LESS = 116, OP_LESS_OR_EQUAL = 120,
-  OP_IF = 204, OP_IF_NULL = 220, OP_IS_NULL = 224, OP_CAST_QUIET = 265, OP_LENGTH = 400, OP_LTRIM = 404, OP_RTRIM = 408, OP_TRIM = 412, OP_TOUPPER = 416, OP_SUBSTRING = 427, OP_STRING_OFFSET = 476,
-  OP_STRING_REPLACE = 480, OP_PARSE_STRING_QUIET = 437, OP_PARSE_STRING_NULLING = 438
-};
-
 // machine type classes
 enum MT { M_I32, M_U32, M_I64, M_U64, M_F32, M_F64, M_B8, M_BAD };
 static MT mtype(int dtype) {
@@ -139,35 +121,11 @@ class Emitter {
     P->gathers.push_back(g);
     return (int)P->gathers.size() - 1;
   }
-  // a table over the plan's STRING dictionary (string_fn_kernels.hip): shares the join gathers' slots; equal
-  // (function, needle, fold) nodes share one table
-  int table_slot(int fn, int32_t needle_code, bool fold) {
-    for (size_t i = 0; i < P->gathers.size(); ++i) {
-      const JoinGather& t = P->gathers[i];
-      if (t.join_id == JOIN_GATHER_DICT_TABLE && t.fn == fn && t.needle_code == needle_code && t.fold == fold) return (int)i;
-    }
-    JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.fn = fn; g.needle_code = needle_code; g.fold = fold;
-    P->gathers.push_back(g);
-    return (int)P->gathers.size() - 1;
-  }
-  // ... and the table of a string-producing function, keyed by (function, position, length): the plan's closed dictionary brings it
-  int producer_slot(int fn, int64_t pos, int64_t len, bool has_len) {
-    for (size_t i = 0; i < P->gathers.size(); ++i) {
-      const JoinGather& t = P->gathers[i];
-      if (t.join_id == JOIN_GATHER_DICT_TABLE && t.fn == fn && t.pos == pos && t.len == len && t.has_len == has_len) return (int)i;
-    }
-    JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.fn = fn; g.pos = pos; g.len = len; g.has_len = has_len;
-    P->gathers.push_back(g);
-    return (int)P->gathers.size() - 1;
-  }
-  // ... and the PARSE_STRING tables of a target type (values + failure bytes, string_parse_kernels.hip): ONE slot per type, whichever
-  // of ParseStringQuiet / ParseStringNulling asks
-  int parse_slot(int to_type) {
-    for (size_t i = 0; i < P->gathers.size(); ++i) {
-      const JoinGather& t = P->gathers[i];
-      if (t.join_id == JOIN_GATHER_DICT_TABLE && t.fn == DICT_FN_PARSE && t.to_type == to_type) return (int)i;
-    }
-    JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.fn = DICT_FN_PARSE; g.to_type = to_type;
+  // a table over the plan's STRING dictionary (DictTableSpec): shares the join gathers' slots; nodes of equal specs share one table
+  int dict_table_slot(const DictTableSpec& spec) {
+    for (size_t i = 0; i < P->gathers.size(); ++i)
+      if (P->gathers[i].join_id == JOIN_GATHER_DICT_TABLE && P->gathers[i].table == spec) return (int)i;
+    JoinGather g; g.join_id = JOIN_GATHER_DICT_TABLE; g.rhs_col = 0; g.is_null_mask = false; g.table = spec;
     P->gathers.push_back(g);
     return (int)P->gathers.size() - 1;
   }
@@ -587,13 +545,13 @@ Status Emitter::value(const BExprP& e, Val* out) {
           v.null = base_null;
         } break;
         case OP_LENGTH: case OP_STRING_OFFSET: {
-          // f(s) = T[code(s)]: the table is built once per distinct value before the first run (runtime.cpp: dictionary tables);
+          // f(s) = T[code(s)]: the table is built once per distinct value before the first run (string_dict.cpp: DictTables);
           // the NULL mask is the haystack's own -- T has no NULLs and a code is never VM_NONE (NULL rows and the rows past the end of
           // the last tile carry code 0, and T always has an entry 0)
           const bool offset = e->op == OP_STRING_OFFSET;
           if (offset && e->args[1]->kind == BExpr::NULLCONST) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // NULL needle
           const int code = materialize(a[0]);
-          const int slot = table_slot(offset ? OP_STRING_OFFSET : OP_LENGTH, offset ? (int32_t)(uint32_t)e->args[1]->bits : 0, offset && e->bits != 0);
+          const int slot = dict_table_slot(DictTableSpec::computed(e->op, offset ? (int32_t)(uint32_t)e->args[1]->bits : 0, e->bits != 0));
           v.reg = new_reg(4);
           LInstr& i = emit(VM_GATHER_32); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot;
           v.null = a[0].null;
@@ -606,9 +564,9 @@ Status Emitter::value(const BExprP& e, Val* out) {
           // STRING_REPLACE's step carries the codes of its constant needle and substitute in pos / len.
           if (e->str_null) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // NULL position / length / needle / substitute
           const int code = materialize(a[0]);
-          const int slot = producer_slot(e->op, e->str_pos, e->str_len, e->str_has_len);
-          ssgpu_string_step step; step.fn = e->op; step.has_len = e->str_has_len ? 1 : 0; step.pos = e->str_pos; step.len = e->str_len;
-          P->string_steps.push_back(step);
+          const DictTableSpec spec = DictTableSpec::producer(e->op, e->str_pos, e->str_len, e->str_has_len);
+          const int slot = dict_table_slot(spec);
+          P->string_steps.push_back(spec.step());
           v.reg = new_reg(4);
           LInstr& i = emit(VM_GATHER_32); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot;
           v.null = a[0].null;
@@ -619,7 +577,7 @@ Status Emitter::value(const BExprP& e, Val* out) {
           // VM_NONE (NULL rows and the rows past the last tile carry code 0; both tables have an entry 0), so GATHER_NULL says F and nothing else.
           if (e->str_null) { v.imm = true; v.bits = 0; v.null = const_null_reg(); break; }   // PARSE_STRING(NULL)
           const int code = materialize(a[0]);
-          const int slot = parse_slot(e->dtype);
+          const int slot = dict_table_slot(DictTableSpec::parse(e->dtype));
           v.reg = new_reg(v.width);
           { LInstr& i = emit(v.width == 8 ? VM_GATHER_64 : v.width == 4 ? VM_GATHER_32 : VM_GATHER_8); i.dst = v.reg; i.a = code; i.imm = (uint64_t)slot; }
           v.null = a[0].null;

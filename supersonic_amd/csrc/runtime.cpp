@@ -9,14 +9,13 @@
 #include <atomic>
 #include <chrono>
 #include <map>
-#include <tuple>
 #include <set>
 #include <mutex>
 #include <stdio.h>
 #include <stdlib.h>
-#include <locale.h>
 #include <string.h>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <string>
 #include <unistd.h>
@@ -26,138 +25,21 @@
 #include <deque>
 #include <functional>
 
-#include "engine.h"
+#include "runtime_internal.h"
 
 using namespace ssgpu;
 
-#define HIP_TRY(ctx, expr)                                                          \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) {                                                          \
-      (ctx)->err = _e == hipErrorOutOfMemory ? std::string("Memory exceeded: ") + #expr : std::string(#expr) + ": " + hipGetErrorString(_e); \
-      return _e == hipErrorOutOfMemory ? SSGPU_ERROR_MEMORY_EXCEEDED : SSGPU_ERROR_HIP; \
-    }                                                                                \
-  } while (0)
-
 static bool trace_on() { static const bool on = getenv("SSGPU_TRACE") != nullptr; return on; }   // development: shape decisions and fallbacks on stderr
-struct ssgpu_ctx {
-  // plans and blocks hold a reference: the context outlives them whatever order a garbage-collected host
-  // destroys the handles in (ssgpu_ctx_destroy only drops the owner's reference)
-  std::atomic<int> refs{1};
-  int device = -1;
-  hipStream_t stream = nullptr, copy_stream = nullptr;
-  // ssgpu_block_upload copies on the copy stream; a run that reads the block through raw column pointers (ssgpu_plan_run / ssgpu_expr_evaluate
-  // with ssgpu_block_column's answers, instead of ssgpu_plan_run_block) used to race with those copies -- seen as a wrong Evaluate result
-  // of the C++ facade on a loaded GPU.  Every upload raises the flag; the next run of ANY plan of the context orders its stream behind the copies.
-  std::atomic<bool> copy_pending{false};
-  hipEvent_t copy_ev = nullptr;
-  bool own_stream = false;
-  int cu_count = 0;
-  std::string err;
-  LowerOptions opt;
-  int64_t grid_limit = 0;        // 0 = CUs * residency
-  int64_t out_arena = 1;         // 1: a stage's large result is one allocation with skewed column bases (ensure_out_cols), 0: a buffer per column
-  int64_t tile_map = 1;          // which tile a workgroup of a pipeline launch takes: 0 = its block index (neighbouring tiles on different XCDs), 1 = XCD-contiguous
-                                 // chunks for launches that WRITE compacted / materialised rows (vm.h VM_FLAG_XCD_CHUNKS: lines two tiles share merge in one L2), 2 = for every launch
-  int64_t wgs_per_cu = 3;        // resident 4-wave workgroups per CU (<= 4 at the kernel's 128-VGPR budget; 3 streams best)
-  int64_t group_capacity = 1 << 18;
-  int64_t group_local = 1;       // 0: never use the LDS pre-aggregation table
-  int64_t group_partition = 1;   // 0: never switch to the partitioned GroupAggregate; 2: always use it
-  int64_t part_n = 0;            // initial number of hash partitions (0 = 512)
-  int64_t part_wgs_per_cu = 0;   // resident workgroups per CU of the scatter pass (0 = wgs_per_cu)
-  int64_t part_lds_target = 0;   // LDS target of the scatter pass's tile (0 = lds_target_bytes)
-  int64_t sort_records = 1;      // 0: always gather payload columns one by one
-  int64_t sort_hybrid = 1;       // 0: never take the high-half-first shortcut for wide keys
-  int64_t group_slab = 1;        // 0: never take the slab form of the partitioned GroupAggregate
-  int64_t group_scout = 1;       // 0: no scout run ahead of the first large GroupAggregate run (see run_group_agg)
-  int64_t group_scout_rows = 8 << 20;   // ... "large": inputs of at least this many rows (a smaller value helps first runs and costs steady ones: see run_group_agg)
-  int64_t group_resident = 1;    // 0: plain stages take the slab form through scatter + aggregation like every other stage (tests, A/B)
-  int64_t group_dense = 1;       // 0: never index group tables by the keys' value ranges (dense slots, see DenseState); SSGPU_GROUP_DENSE sets the process default
-  int64_t dense_parts = 0;       // partitions of the dense partitioned shape (0 = 256, more -- the next power of two -- when the tables would outgrow 80 KiB)
-  int64_t dense_min_rows = 1 << 16;   // inputs below this many rows never look for dense ranges (tests lower it to reach the dense kernels with small inputs)
-  int64_t async_handoff = 1;     // 0: every stage hand-off reads the row count on the host (a stream synchronise), even where the next stage could take it from the device
-  int64_t lazy_feedback = 0;     // 1: a GroupAggregate in its steady state leaves its overflow / feedback words on the stream instead of reading them back
-                                 // at the end of every run, and a run may be REPEATED from the caller's input columns when its result is first touched
-                                 // (an overflow seen late, a NaN in a floating MIN / MAX).  Off by default (round 5): ssgpu_plan_run returns with every
-                                 // such decision made -- the input may be released or overwritten once the run has been synchronised.  Callers that
-                                 // step a plan without touching the host opt in (distributed.py, sharded.h, bench.py) and keep their input alive.
-  int64_t part_prefetch = 1;     // specialised partition aggregation, records of <= 6 words: the loads of trip k + 1 are issued before trip k's LDS atomics
-  int64_t fuse_emit = 1;         // ScalarAggregate: the finish launch also emits the result row (0: a launch of its own, as until round 6)
-  int64_t pscat_pipe = 1;        // specialised plain scatter: the software-pipelined form (tile k + 1 loaded, ranked and reserved while tile k is staged and flushed)
-  int64_t pscat_threads = 0, pscat_rows = 0, pscat_wgs = 0;   // launch shape of the plain scatter (0: 1024 threads x 2 rows, one workgroup per CU; ssgpu_part_scatter_plain_geom)
-  int64_t part_plain = 1;        // 0: never run the partition scatter as its own kernel (plain stages), always as the VM program
-  int64_t sort_compact = 1;      // 0: never sort (high half << 32 | row id) words instead of (key, row id) pairs
-  int64_t sort_hi_digits = 4;    // high digits the hybrid sort passes over before fixing ties: 2..4, 0 = by row count
-  int64_t part_agg_lds = 0;      // LDS bytes of phase 2's workgroup (0 = 80 KiB: two workgroups per CU)
-  int64_t profile = 1;           // record HIP events around kernels
-  int64_t profile_total = 1;     // ... and around the whole run (kernel_ms); 0 keeps only the dominant kernel's pair
-  int64_t debug_timing = 0;
-  int64_t specialize = 3;        // plans created on this context run kernels specialised for them by runtime compilation (rtc.cpp):
-                                 // 1 = yes, compiled when a kernel shape is first launched (the first run; a later run only if run
-                                 // feedback moves a GroupAggregate to another execution shape) -- the run WAITS for the compiler;
-                                 // 2 = where such a kernel EXISTS already -- loaded in this process or stored in the on-disk cache
-                                 // by any earlier one -- and never compiled; 3 (the default) = like 2, and a kernel that is missing
-                                 // when a run over >= specialize_min_rows rows wants it is compiled by the library's one worker
-                                 // thread: no run ever waits for the compiler, the plan's later runs (and, through the disk cache,
-                                 // later processes) pick the kernel up; 0 (and the legacy -1) = only plans that ask for it with
-                                 // ssgpu_plan_specialize.
-  int64_t specialize_min_rows = 1 << 22;   // option 3: runs over fewer input rows never start a compilation (their kernels take microseconds)
-};
 
-// Device memory a plan holds, against its soft quota (ssgpu_plan_set_memory_limit = MemoryLimit, memory.h:465): every
-// DevBuf (re)allocated while a plan runs is charged to that plan; a request beyond the quota fails like an allocation the
-// device cannot serve, which HIP_TRY turns into SSGPU_ERROR_MEMORY_EXCEEDED.
-struct MemQuota { int64_t limit = -1; int64_t used = 0; };
-static thread_local MemQuota* g_quota = nullptr;
-struct QuotaScope { MemQuota* saved; explicit QuotaScope(MemQuota* q) : saved(g_quota) { g_quota = q; } ~QuotaScope() { g_quota = saved; } };
+thread_local MemQuota* g_quota = nullptr;
 
 // process-wide accounting of what the library holds (ssgpu_memory_stats): the per-process measure behind the
 // "repeated runs do not grow memory" contract (expression_test_helper.cc:213-245 watches its allocator the same way)
 static std::atomic<uint64_t> g_dict_gen{0};   // stamps of ssgpu_plan_set_dict calls (ssgpu_plan::dict_gen)
-static std::atomic<long long> g_dev_bytes{0}, g_pinned_bytes{0}, g_live_plans{0}, g_live_blocks{0}, g_events{0};
+std::atomic<long long> g_dev_bytes{0}, g_pinned_bytes{0};
+static std::atomic<long long> g_live_plans{0}, g_live_blocks{0}, g_events{0};
 
-// A small pool of device blocks between plans.  The reference's usage model is a cursor per query, drained once
-// (test/guide/group_sort.cc:166,223): every query's first -- and only -- run would pay a hipMalloc per buffer (two dozen for a
-// GroupAggregate, each 50 - 300 us: more than the kernels of a million-row input).  Blocks of a DESTROYED plan (its stream has been
-// drained: nothing in flight can touch them) are parked here instead of freed, and the next plan's DevBuf::ensure takes one that
-// fits (within 2x; small blocks by 4 KiB class) before it asks the driver.  Bounded: SSGPU_POOL_MB (default 4096, 0 = off) and
-// 4096 blocks; what is parked still counts as held by the library (ssgpu_memory_stats.device_bytes).
-struct DevPool {
-  std::mutex m;
-  std::multimap<size_t, std::pair<void*, int>> blocks;   // capacity -> (pointer, device)
-  size_t bytes = 0;
-  size_t limit() { static const size_t v = [] { const char* e = getenv("SSGPU_POOL_MB"); return (size_t)(e ? atoll(e) : 4096) << 20; }(); return v; }
-  // The device of a parked block is the device of the POINTER (hipPointerGetAttributes), never the calling thread's current
-  // device: ssgpu_plan_destroy may run while another context's device is current (round-5 advice).
-  bool park(void* p, size_t cap) {
-    if (limit() == 0) return false;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const int dev = attr.device;
-    std::lock_guard<std::mutex> lock(m);
-    if (bytes + cap > limit() || blocks.size() >= 4096) return false;
-    blocks.emplace(cap, std::make_pair(p, dev)); bytes += cap;
-    return true;
-  }
-  void* take(size_t want, size_t* cap) {
-    int dev = 0;
-    if (limit() == 0 || hipGetDevice(&dev) != hipSuccess) return nullptr;
-    const size_t most = want <= 4096 ? 4096 : want * 2;
-    std::lock_guard<std::mutex> lock(m);
-    for (auto it = blocks.lower_bound(want); it != blocks.end() && it->first <= most; ++it)
-      if (it->second.second == dev) { void* p = it->second.first; *cap = it->first; bytes -= it->first; blocks.erase(it); return p; }
-    return nullptr;
-  }
-  // frees every parked block (dev < 0) or those of one device; returns the bytes given back to the driver
-  size_t trim(int dev);
-  size_t parked(int dev) {
-    std::lock_guard<std::mutex> lock(m);
-    size_t n = 0;
-    for (auto& b : blocks) if (dev < 0 || b.second.second == dev) n += b.first;
-    return n;
-  }
-};
-static DevPool g_pool;
+DevPool g_pool;
 size_t DevPool::trim(int dev) {
   std::vector<std::pair<void*, size_t>> out;
   {
@@ -170,61 +52,7 @@ size_t DevPool::trim(int dev) {
   return freed;
 }
 static std::atomic<int> g_device_contexts{0};          // contexts with a device alive in this process: the last one to go empties the pool
-static thread_local bool tls_park_released = false;   // set while a plan whose stream has been drained is being destroyed
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool view = false;      // p points into somebody else's allocation (a block's arena): never freed, never regrown here
-  MemQuota* q = nullptr;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p && !view) {
-      if (q) q->used -= (int64_t)cap;
-      if (!(tls_park_released && g_pool.park(p, cap))) { (void)hipFree(p); g_dev_bytes.fetch_sub((long long)cap); }
-    }
-    p = nullptr; cap = 0; q = nullptr; view = false;
-  }
-  void set_view(void* ptr, size_t bytes) { release(); p = ptr; cap = bytes; view = true; }
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (view) return hipErrorInvalidValue;    // (a view has the size its owner gave it)
-    size_t want = std::max<size_t>(bytes, 256);
-    MemQuota* Q = g_quota;
-    if (Q && Q->limit >= 0 && Q->used - (q == Q ? (int64_t)cap : 0) + (int64_t)want > Q->limit) return hipErrorOutOfMemory;
-    static const bool trace = getenv("SSGPU_TRACE") != nullptr;   // development: (re)allocations of large buffers are slow and must not sit in a steady state
-    if (trace && want >= (64u << 20)) fprintf(stderr, "[ssgpu trace] device buffer %zu -> %zu MiB\n", cap >> 20, want >> 20);
-    release();
-    size_t pooled_cap = 0;
-    // (a plan under a quota allocates exactly what it asks for; a pooled block is still counted in g_dev_bytes)
-    if (void* pooled = (Q && Q->limit >= 0) ? nullptr : g_pool.take(want, &pooled_cap)) { p = pooled; cap = pooled_cap; q = Q; if (q) q->used += (int64_t)cap; return hipSuccess; }
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipErrorOutOfMemory) {
-      // the driver is out of memory while blocks of destroyed plans sit in the pool: give those back and ask once more
-      (void)hipGetLastError();
-      int dev = -1;
-      if (hipGetDevice(&dev) == hipSuccess && g_pool.trim(dev) > 0) e = hipMalloc(&p, want);
-    }
-    if (e == hipSuccess) { cap = want; q = Q; g_dev_bytes.fetch_add((long long)want); if (q) q->used += (int64_t)want; } else p = nullptr;
-    return e;
-  }
-  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-struct PinnedBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~PinnedBuf() { drop(); }
-  void drop() { if (p) { (void)hipHostFree(p); g_pinned_bytes.fetch_sub((long long)cap); } p = nullptr; cap = 0; }
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    drop();
-    size_t want = std::max<size_t>(bytes, 256);
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e == hipSuccess) { cap = want; g_pinned_bytes.fetch_add((long long)want); } else p = nullptr;
-    return e;
-  }
-};
+thread_local bool tls_park_released = false;
 
 struct OutCol { DevBuf data, nulls; bool nullable = false; uint32_t width = 8; };   // (views into StageExec::out_arena for large results)
 
@@ -348,9 +176,6 @@ struct StageExec {
   uint32_t steady_bypass = 0;   // direct shape: rows that bypassed the LDS table in the last synchronous run
 };
 
-// A STRING dictionary packed for the device: `offs[n + 1]` into one byte heap (STRFN_HEAP_PAD zero bytes behind it)
-struct DictDevice { DevBuf offs, heap; uint64_t n = 0; };
-
 struct ssgpu_result {
   ssgpu_plan* plan = nullptr;
   std::vector<PinnedBuf> host_data, host_nulls;
@@ -396,24 +221,10 @@ struct ssgpu_plan {
   bool deferred = false;        // some stage's run feedback has not been looked at yet (settle_plan)
   bool nan_seen = false;        // the last run met a NaN in a floating MIN / MAX (check_error_flags)
   const ssgpu_dict* dict = nullptr;   // the plan's STRING dictionary (ssgpu_plan_set_dict): CONCAT prints STRING inputs through it
-  // Tables over that dictionary (Program::gathers of JOIN_GATHER_DICT_TABLE; string_fn_kernels.hip): the dictionary packed and uploaded
-  // once, one table of 4-byte entries per (function, needle code, fold).  Dictionaries are immutable, so the tables are built lazily
-  // before the first run that needs them and again when the plan is handed another dictionary (dict_gen: the stamp of the
-  // ssgpu_plan_set_dict call, so that a new dictionary at a freed one's address is not mistaken for it); freed with the plan.
-  // The table of a string-producing node (LTRIM ... SUBSTRING) is not computed here: the plan's CLOSED dictionary brings it along
-  // (ssgpu_dict_close) and ensure_dict_tables uploads it, after checking that the dictionary was closed under the plan's steps.
+  // the tables over that dictionary that the plan's programs gather from (string_dict.cpp), rebuilt when dict_gen moves: the stamp of
+  // the ssgpu_plan_set_dict call
   uint64_t dict_gen = 0;
-  struct DictTables {
-    bool built = false; uint64_t built_gen = 0; const ssgpu_dict* built_for = nullptr;
-    DictDevice dev; DevBuf needle;
-    typedef std::tuple<int, int32_t, bool, int64_t, int64_t, bool, int> Key;   // function, needle code, fold; a producer's position, length, has_len; PARSE_STRING's target type
-    static Key key(const JoinGather& g) { return Key(g.fn, g.needle_code, g.fold, g.pos, g.len, g.has_len, g.to_type); }
-    std::map<Key, DevBuf> tables;
-    // PARSE_STRING (fn DICT_FN_PARSE, string_parse_kernels.hip): `tables` holds the values, this the failure bytes the slot's is_null points
-    // at; host_resolved: the FLOAT / DOUBLE entries the device left to the host's strtof / strtod when the tables were last built
-    std::map<Key, DevBuf> failed;
-    int64_t host_resolved = 0;
-  } dict_tables;
+  DictTables dict_tables;
   std::vector<ssgpu_column> last_cols; int64_t last_base = 0; bool last_partial = false;   // the last run's input (a deferred overflow repeats it)
   // ssgpu_plan_run_host: two alternating sets of device columns the host rows are staged through, and the chunks' partial states
   std::vector<DevBuf> host_stage_data[2], host_stage_nulls[2];
@@ -477,6 +288,18 @@ static const Stage::ConcatCol* concat_of(const ssgpu_plan* p, int32_t col) {
   if (p->stages.empty()) return nullptr;
   for (auto& cc : p->stages.back().concat) if (cc.out_col == col) return &cc;
   return nullptr;
+}
+
+// every program of a stage, in the order the runtime looks at them
+static std::array<const Program*, 3> stage_programs(const Stage& st) { return {&st.main, &st.count_pass, &st.part_scatter}; }
+// f(spec) for the tables over the STRING dictionary that the plan's programs gather from (JOIN_GATHER_DICT_TABLE), in program order: once
+// per gather, or -- `distinct` -- once per spec
+template <typename F> static void for_each_dict_table(const ssgpu_plan* p, bool distinct, F f) {
+  std::set<DictTableSpec> seen;
+  for (auto& st : p->stages)
+    for (const Program* pr : stage_programs(st))
+      for (auto& g : pr->gathers)
+        if (g.join_id == JOIN_GATHER_DICT_TABLE && (!distinct || seen.insert(g.table).second)) f(g.table);
 }
 
 extern "C" {
@@ -664,65 +487,6 @@ static bool read_slab(FILE* f, char* dst, size_t bytes) {
 // The domain is the block's STRING columns end to end (column k's row r is domain row k x rows + r).  `lens` holds domain + 1
 // words: the byte lengths, scanned here into offsets into `heap`; `dnull` one NULL byte per domain row.  Runs on the copy
 // stream, writes the codes into the block's STRING columns and gives the block its dictionary.
-static const int64_t kMaxStringDomain = int64_t(1) << 30;   // the table's slot numbers stay 32-bit
-// The device part, for any domain of n rows (`lens`: n + 1 words, `dnull`: n bytes): the distinct values sorted in StringPiece order
-// -- on the device as out_off[D + 1] / out_heap (`heap_pad` bytes of slack behind the values, for readers of aligned words) and copied
-// back once into off_h / heap_h -- and, for every target, codes[first + r] of its `rows` domain rows written to dst (0 for a NULL row).
-// `scanned`: lens already holds the offsets (the caller needed the total to size the heap).  Returns with the stream idle.
-struct DomainCodes { int32_t* dst; uint64_t first, rows; };
-static int encode_domain(ssgpu_ctx* c, hipStream_t s, const uint8_t* bytes, uint64_t* lens, bool scanned, const uint8_t* dnull, uint64_t n,
-                         const std::vector<DomainCodes>& targets, uint64_t heap_pad, std::vector<uint64_t>* off_h_out, std::vector<char>* heap_h_out,
-                         uint32_t* D_out, DevBuf& out_off, DevBuf& out_heap) {
-  std::vector<uint64_t>& off_h = *off_h_out;
-  std::vector<char>& heap_h = *heap_h_out;
-  off_h.assign(1, 0);
-  heap_h.clear();
-  uint32_t D = 0;
-  if (n) {
-    uint64_t cap = 64, np2 = 1;
-    while (cap < 2 * n) cap <<= 1;
-    while (np2 < n) np2 <<= 1;
-    DevBuf partials, hashes, table, row_slot, flags, d_slot, d_off, d_len, d_key, d_idx, slot_rank;
-    const bool alloc_ok =
-        partials.ensure(ssgpu_str_scan_partials(n) * 8) == hipSuccess && hashes.ensure(n * 8) == hipSuccess && table.ensure(cap * 8) == hipSuccess &&
-        row_slot.ensure(n * 4) == hipSuccess && flags.ensure(8) == hipSuccess && d_slot.ensure(n * 4) == hipSuccess && d_off.ensure(n * 8) == hipSuccess &&
-        d_len.ensure(n * 8) == hipSuccess && d_key.ensure(np2 * 8) == hipSuccess && d_idx.ensure(np2 * 4) == hipSuccess &&
-        slot_rank.ensure(cap * 4) == hipSuccess && out_off.ensure((n + 1) * 8) == hipSuccess;
-    if (!alloc_ok) { c->err = "Memory exceeded: the STRING dictionary's device tables"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
-    const uint64_t* offs = lens;
-    if (!scanned) HIP_TRY(c, ssgpu_launch_str_scan(lens, n, partials.as<uint64_t>(), s));
-    HIP_TRY(c, ssgpu_launch_str_hash(bytes, offs, dnull, n, hashes.as<uint64_t>(), s));
-    HIP_TRY(c, hipMemsetAsync(table.p, 0, cap * 8, s));
-    HIP_TRY(c, hipMemsetAsync(flags.p, 0, 8, s));
-    HIP_TRY(c, ssgpu_launch_str_insert(bytes, offs, dnull, hashes.as<uint64_t>(), n, table.as<uint64_t>(), cap, row_slot.as<uint32_t>(),
-                                       flags.as<uint32_t>() + 1, s));
-    HIP_TRY(c, ssgpu_launch_str_compact(table.as<uint64_t>(), cap, bytes, offs, flags.as<uint32_t>(), d_slot.as<uint32_t>(), d_off.as<uint64_t>(),
-                                        d_len.as<uint64_t>(), d_key.as<uint64_t>(), d_idx.as<uint32_t>(), s));
-    uint32_t fl[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(fl, flags.p, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (fl[1]) { c->err = "STRING dictionary: hash table overflow"; return SSGPU_ERROR_UNKNOWN; }
-    D = fl[0];
-    uint64_t p2 = 1;
-    while (p2 < D) p2 <<= 1;
-    HIP_TRY(c, ssgpu_launch_str_sort(d_key.as<uint64_t>(), d_idx.as<uint32_t>(), D, D ? p2 : 0, bytes, d_off.as<uint64_t>(), d_len.as<uint64_t>(), s));
-    HIP_TRY(c, ssgpu_launch_str_rank(d_idx.as<uint32_t>(), d_slot.as<uint32_t>(), d_len.as<uint64_t>(), D, slot_rank.as<int32_t>(), out_off.as<uint64_t>(), s));
-    HIP_TRY(c, ssgpu_launch_str_scan(out_off.as<uint64_t>(), D, partials.as<uint64_t>(), s));
-    for (const DomainCodes& t : targets)
-      HIP_TRY(c, ssgpu_launch_str_codes(row_slot.as<uint32_t>() + t.first, dnull + t.first, slot_rank.as<int32_t>(), t.rows, t.dst, s));
-    off_h.resize((size_t)D + 1);
-    HIP_TRY(c, hipMemcpyAsync(off_h.data(), out_off.p, ((size_t)D + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (out_heap.ensure(std::max<uint64_t>(off_h[D], 1) + heap_pad) != hipSuccess) { c->err = "Memory exceeded: the STRING dictionary's values"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
-    if (heap_pad) HIP_TRY(c, hipMemsetAsync(static_cast<char*>(out_heap.p) + off_h[D], 0, heap_pad, s));
-    HIP_TRY(c, ssgpu_launch_str_gather(bytes, d_off.as<uint64_t>(), d_idx.as<uint32_t>(), out_off.as<uint64_t>(), D, out_heap.as<uint8_t>(), s));
-    heap_h.resize((size_t)off_h[D]);
-    if (off_h[D]) HIP_TRY(c, hipMemcpyAsync(heap_h.data(), out_heap.p, (size_t)off_h[D], hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-  }
-  *D_out = D;
-  return SSGPU_OK;
-}
 static int encode_string_domain(ssgpu_ctx* c, ssgpu_block* b, const std::vector<int>& scols, DevBuf& heap, DevBuf& lens, DevBuf& dnull) {
   const uint64_t rows = (uint64_t)b->rows, n = rows * scols.size();
   std::vector<uint64_t> off_h;
@@ -1119,32 +883,9 @@ int ssgpu_plan_attr(const ssgpu_plan* p, int32_t i, ssgpu_attr* out) {
 }
 const char* ssgpu_plan_describe(ssgpu_plan* p) {
   if (!p) return "";
-  // one line per table over the STRING dictionary: function, needle (its length once the dictionary is known), case folding
-  std::set<ssgpu_plan::DictTables::Key> seen;
+  // one line per table over the STRING dictionary
   std::string lines;
-  for (auto& st : p->stages)
-    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
-      for (auto& g : pr->gathers) {
-        if (g.join_id != JOIN_GATHER_DICT_TABLE || !seen.insert(ssgpu_plan::DictTables::key(g)).second) continue;
-        if (is_string_producer(g.fn)) {
-          lines += std::string("dictionary table: ") + (g.fn == 404 ? "LTRIM" : g.fn == 408 ? "RTRIM" : g.fn == 412 ? "TRIM" : g.fn == 416 ? "TO_UPPER" : g.fn == 480 ? "STRING_REPLACE" : "SUBSTRING");
-          if (g.fn == 480) lines += " needle code " + std::to_string(g.pos) + " substitute code " + std::to_string(g.len);
-          if (g.fn == 427) lines += " position " + std::to_string(g.pos) + (g.has_len ? " length " + std::to_string(g.len) : std::string(" to the end"));
-          lines += " (codes of the closed dictionary)\n";
-          continue;
-        }
-        if (g.fn == DICT_FN_PARSE) {
-          lines += std::string("dictionary table: PARSE_STRING to ") + dtype_name(g.to_type) + " (values and failure bytes)";
-          if (p->dict_tables.built && dtype_is_float(g.to_type)) lines += " host-resolved entries of the plan's floating tables: " + std::to_string(p->dict_tables.host_resolved);
-          lines += "\n";
-          continue;
-        }
-        if (g.fn != 476) { lines += "dictionary table: LENGTH\n"; continue; }
-        const char* bytes = nullptr; int32_t len = 0;
-        lines += "dictionary table: STRING_OFFSET needle code " + std::to_string(g.needle_code) +
-                 (p->dict && ssgpu_dict_decode(p->dict, g.needle_code, &bytes, &len) == SSGPU_OK ? " length " + std::to_string(len) : std::string(" length unknown (no dictionary yet)")) +
-                 " fold " + (g.fold ? "1" : "0") + "\n";
-      }
+  for_each_dict_table(p, true, [&](const DictTableSpec& spec) { lines += p->dict_tables.describe(spec, p->dict); });
   if (lines.empty()) return p->describe.c_str();
   p->describe_full = p->describe + lines;
   return p->describe_full.c_str();
@@ -1334,176 +1075,25 @@ int build_joins(ssgpu_plan* p, Stage& st, StageExec& ex) {
   }
   return SSGPU_OK;
 }
-// ---- tables over the STRING dictionary (string_fn_kernels.hip) ------------------------------------------------------
-int dict_upload(ssgpu_ctx* c, const ssgpu_dict* d, DictDevice* out) {
-  const uint64_t n = (uint64_t)ssgpu_dict_size(d), hb = ssgpu_dict_heap_bytes(d);
-  std::vector<uint64_t> offs(n + 1);
-  std::vector<char> heap(hb + 1);
-  ssgpu_dict_pack(d, offs.data(), heap.data());
-  HIP_TRY(c, out->offs.ensure((n + 1) * 8));
-  HIP_TRY(c, out->heap.ensure(hb + STRFN_HEAP_PAD));
-  HIP_TRY(c, hipMemcpyAsync(out->offs.p, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (hb) HIP_TRY(c, hipMemcpyAsync(out->heap.p, heap.data(), hb, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemsetAsync(static_cast<char*>(out->heap.p) + hb, 0, STRFN_HEAP_PAD, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host copies above go out of scope)
-  out->n = n;
-  return SSGPU_OK;
-}
-// table[c] = fn(value c); an empty dictionary gets ONE entry: NULL rows carry code 0 and the gather still reads table[0]
-int dict_table_build(ssgpu_ctx* c, const DictDevice& D, int fn, const char* needle, uint32_t nlen, bool fold, DevBuf* needle_dev, DevBuf* table) {
-  HIP_TRY(c, table->ensure((size_t)std::max<uint64_t>(D.n, 1) * 4));
-  if (D.n == 0) { HIP_TRY(c, hipMemsetAsync(table->p, 0, 4, c->stream)); return SSGPU_OK; }
-  HIP_TRY(c, needle_dev->ensure(std::max<uint32_t>(nlen, 1)));
-  if (fn == 476 && nlen) HIP_TRY(c, hipMemcpyAsync(needle_dev->p, needle, nlen, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, ssgpu_launch_str_fn(D.heap.as<const uint8_t>(), D.offs.as<const uint64_t>(), D.n, fn, needle_dev->as<const uint8_t>(), fn == 476 ? nlen : 0u,
-                                 fold ? 1 : 0, table->as<uint32_t>(), c->stream));
-  return SSGPU_OK;
-}
-// PARSE_STRING: values[c] = value c parsed as `to_type`, failed[c] = 1 where that parse fails (string_parse_kernels.hip).  The device decides
-// the integer and BOOL targets alone.  Of a FLOAT / DOUBLE table it fills what lies on its exact fast path and marks the rest
-// STRPARSE_HARD; those entries are finished here with the reference's own parser -- glibc strtof / strtod in the C locale on the value's
-// bytes cut at the first 0x00, the value kept whatever the outcome (safe_strtof / safe_strtod, numbers.cc:802-829) -- and both tables
-// patched before anything reads them.  *host_resolved += the number of such entries.  An empty dictionary gets one entry, 0 / not failed.
-static locale_t parse_c_locale() { static locale_t loc = newlocale(LC_ALL_MASK, "C", (locale_t)0); return loc; }
-int dict_parse_build(ssgpu_ctx* c, const DictDevice& D, const ssgpu_dict* d, int to_type, DevBuf* values, DevBuf* failed, int64_t* host_resolved,
-                     hipEvent_t after_kernel = nullptr /* recorded behind the kernel, in front of the host's share */) {
-  const size_t w = (size_t)dtype_width(to_type), n = (size_t)D.n;
-  HIP_TRY(c, values->ensure(std::max<size_t>(n, 1) * w));
-  HIP_TRY(c, failed->ensure(std::max<size_t>(n, 1)));
-  if (n == 0) {
-    HIP_TRY(c, hipMemsetAsync(values->p, 0, w, c->stream)); HIP_TRY(c, hipMemsetAsync(failed->p, 0, 1, c->stream));
-    if (after_kernel) HIP_TRY(c, hipEventRecord(after_kernel, c->stream));
-    return SSGPU_OK;
-  }
-  HIP_TRY(c, ssgpu_launch_str_parse(D.heap.as<const uint8_t>(), D.offs.as<const uint64_t>(), D.n, to_type, values->p, failed->as<uint8_t>(), c->stream));
-  if (after_kernel) HIP_TRY(c, hipEventRecord(after_kernel, c->stream));
-  if (!dtype_is_float(to_type)) return SSGPU_OK;
-  std::vector<uint8_t> f(n);
-  HIP_TRY(c, hipMemcpyAsync(f.data(), failed->p, n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::vector<size_t> hard;
-  for (size_t i = 0; i < n; ++i) if (f[i] == STRPARSE_HARD) hard.push_back(i);
-  if (hard.empty()) return SSGPU_OK;
-  std::vector<char> v(n * w);
-  HIP_TRY(c, hipMemcpyAsync(v.data(), values->p, n * w, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::string text;
-  for (size_t i : hard) {
-    const char* bytes = nullptr; int32_t len = 0;
-    if (ssgpu_dict_decode(d, (int32_t)i, &bytes, &len) != SSGPU_OK) { c->err = "PARSE_STRING: the dictionary lost a value"; return SSGPU_ERROR_UNKNOWN; }
-    text.assign(bytes, (size_t)len);
-    const char* str = text.c_str();   // (cut at the first 0x00 by whoever reads it as a C string)
-    char* end = nullptr;
-    if (to_type == SSGPU_FLOAT) { const float x = strtof_l(str, &end, parse_c_locale()); memcpy(v.data() + i * w, &x, w); }
-    else { const double x = strtod_l(str, &end, parse_c_locale()); memcpy(v.data() + i * w, &x, w); }
-    if (end != str) while (*end == ' ' || (unsigned)(*end - 9) < 5u) ++end;   // ascii_isspace
-    f[i] = (*str != '\0' && *end == '\0') ? 0 : 1;
-  }
-  HIP_TRY(c, hipMemcpyAsync(values->p, v.data(), n * w, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(failed->p, f.data(), n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host copies go out of scope)
-  *host_resolved += (int64_t)hard.size();
-  return SSGPU_OK;
-}
 // the plan's step list (ssgpu_plan_string_steps): the string-producing nodes of every program of every stage, in the order they are evaluated
 static void plan_string_steps(const ssgpu_plan* p, std::vector<ssgpu_string_step>* out) {
   for (auto& st : p->stages)
-    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
+    for (const Program* pr : stage_programs(st))
       out->insert(out->end(), pr->string_steps.begin(), pr->string_steps.end());
 }
-static bool same_step(const ssgpu_string_step& a, const ssgpu_string_step& b) {
-  if (a.fn == 480) return b.fn == 480 && a.pos == b.pos && a.len == b.len;   // needle and substitute: codes of the same dictionary
-  return a.fn == b.fn && (a.fn != 427 || (a.pos == b.pos && (a.has_len != 0) == (b.has_len != 0) && (!a.has_len || a.len == b.len)));
-}
 static bool plan_has_dict_tables(const ssgpu_plan* p) {
-  for (auto& st : p->stages)
-    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
-      for (auto& g : pr->gathers) if (g.join_id == JOIN_GATHER_DICT_TABLE) return true;
-  return false;
+  bool any = false;
+  for_each_dict_table(p, false, [&](const DictTableSpec&) { any = true; });
+  return any;
 }
-// before a run: every table the plan's programs gather from exists and belongs to the plan's current dictionary
+// before a run: every table the plan's programs gather from exists and belongs to the plan's current dictionary (string_dict.cpp)
 int ensure_dict_tables(ssgpu_plan* p) {
-  if (!plan_has_dict_tables(p)) return SSGPU_OK;
-  ssgpu_ctx* c = p->ctx;
-  if (!p->dict) {
-    std::vector<ssgpu_string_step> producers;
-    plan_string_steps(p, &producers);
-    bool parses = false, others = false;
-    for (auto& st : p->stages)
-      for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
-        for (auto& g : pr->gathers) if (g.join_id == JOIN_GATHER_DICT_TABLE) (g.fn == DICT_FN_PARSE ? parses : others) = true;
-    if (parses && !others && producers.empty()) { c->err = "PARSE_STRING of a STRING value needs the plan's dictionary (ssgpu_plan_set_dict)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
-    c->err = producers.empty() ? "LENGTH / STRING_OFFSET / PARSE_STRING of a STRING value need the plan's dictionary (ssgpu_plan_set_dict)"
-                               : "LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING / STRING_REPLACE need the plan's dictionary, closed under the plan's steps (ssgpu_plan_string_steps, "
-                                 "ssgpu_dict_close, ssgpu_plan_set_dict)";
-    return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-  }
-  ssgpu_plan::DictTables& T = p->dict_tables;
-  if (T.built && T.built_for == p->dict && T.built_gen == p->dict_gen) return SSGPU_OK;
-  T.built = false;
-  // String-producing nodes gather from the tables the CLOSED dictionary brings along (ssgpu_dict_close): the run computes nothing, but it
-  // reads no table that is not its own -- the plan's step list must be a subsequence of the list the dictionary was closed under (a later
-  // step's domain contains every earlier one's; the derived plans of chunked execution, the NaN-exact repeat and the skip form hold subsets)
+  if (!plan_has_dict_tables(p) || p->dict_tables.current(p->dict, p->dict_gen)) return SSGPU_OK;
+  std::vector<DictTableSpec> gathers;
+  for_each_dict_table(p, false, [&](const DictTableSpec& spec) { gathers.push_back(spec); });
   std::vector<ssgpu_string_step> steps;
   plan_string_steps(p, &steps);
-  const int32_t dict_steps = ssgpu_dict_step_count(p->dict);
-  { int32_t k = 0;
-    for (const ssgpu_string_step& s : steps) {
-      while (k < dict_steps && !same_step(*ssgpu_dict_step(p->dict, k), s)) ++k;
-      if (k == dict_steps) {
-        c->err = std::string("LTRIM / RTRIM / TRIM / TO_UPPER / SUBSTRING / STRING_REPLACE make STRING values: the plan's dictionary must be closed under the plan's ") +
-                 std::to_string(steps.size()) + " step(s) (ssgpu_plan_string_steps, ssgpu_dict_close, ssgpu_plan_set_dict); this one " +
-                 (dict_steps ? "was closed under another list of " + std::to_string(dict_steps) + " step(s)" : std::string("is not closed"));
-        return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-      }
-      ++k;
-    } }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (an earlier run may still read the tables that are replaced now)
-  T.host_resolved = 0;
-  bool computed = false;   // some table is COMPUTED from the packed dictionary (LENGTH / STRING_OFFSET / PARSE_STRING)
-  for (auto& st : p->stages)
-    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
-      for (auto& g : pr->gathers) computed = computed || (g.join_id == JOIN_GATHER_DICT_TABLE && !is_string_producer(g.fn));
-  int rc = computed ? dict_upload(c, p->dict, &T.dev) : SSGPU_OK;
-  if (rc != SSGPU_OK) return rc;
-  const int32_t n = ssgpu_dict_size(p->dict);
-  std::set<ssgpu_plan::DictTables::Key> parse_built;
-  for (auto& st : p->stages)
-    for (const Program* pr : {&st.main, &st.count_pass, &st.part_scatter})
-      for (auto& g : pr->gathers) {
-        if (g.join_id != JOIN_GATHER_DICT_TABLE) continue;
-        if (is_string_producer(g.fn)) {
-          // the table of the LAST step with this key: its domain is the largest.  An empty dictionary still gets one entry, 0.
-          DevBuf& table = T.tables[ssgpu_plan::DictTables::key(g)];
-          ssgpu_string_step want; want.fn = g.fn; want.has_len = g.has_len ? 1 : 0; want.pos = g.pos; want.len = g.len;
-          int32_t k = dict_steps - 1;
-          while (k >= 0 && !same_step(*ssgpu_dict_step(p->dict, k), want)) --k;
-          if (k < 0) { c->err = "internal: a producer table without its step"; return SSGPU_ERROR_UNKNOWN; }
-          HIP_TRY(c, table.ensure((size_t)std::max<int32_t>(n, 1) * 4));
-          if (n) HIP_TRY(c, hipMemcpyAsync(table.p, ssgpu_dict_step_table_data(p->dict, k), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-          else HIP_TRY(c, hipMemsetAsync(table.p, 0, 4, c->stream));
-          continue;
-        }
-        if (g.fn == DICT_FN_PARSE) {   // the same (target type) slot in several programs: built once
-          const ssgpu_plan::DictTables::Key key = ssgpu_plan::DictTables::key(g);
-          if (!parse_built.insert(key).second) continue;
-          rc = dict_parse_build(c, T.dev, p->dict, g.to_type, &T.tables[key], &T.failed[key], &T.host_resolved);
-          if (rc != SSGPU_OK) return rc;
-          p->counters.n_launches += 1;
-          continue;
-        }
-        const char* needle = ""; int32_t nlen = 0;
-        if (g.fn == 476 && ssgpu_dict_decode(p->dict, g.needle_code, &needle, &nlen) != SSGPU_OK) {
-          c->err = "STRING_OFFSET: the needle's code " + std::to_string(g.needle_code) + " is outside the plan's dictionary of " + std::to_string(n) + " values (ssgpu_plan_set_dict)";
-          return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-        }
-        rc = dict_table_build(c, T.dev, g.fn, needle, (uint32_t)nlen, g.fold, &T.needle, &T.tables[ssgpu_plan::DictTables::key(g)]);
-        if (rc != SSGPU_OK) return rc;
-        p->counters.n_launches += 1;
-      }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  T.built = true; T.built_for = p->dict; T.built_gen = p->dict_gen;
-  return SSGPU_OK;
+  return p->dict_tables.build(p->ctx, p->dict, p->dict_gen, gathers, steps, &p->counters.n_launches);
 }
 
 void apply_joins(const ssgpu_plan* p, const StageExec& ex, const Program& prog, VmParams* P) {
@@ -1511,12 +1101,7 @@ void apply_joins(const ssgpu_plan* p, const StageExec& ex, const Program& prog, 
   for (size_t g = 0; g < prog.gathers.size() && g < VM_MAX_JOIN_COLS; ++g) {
     const JoinGather& jg = prog.gathers[g];
     if (jg.join_id == JOIN_GATHER_DICT_TABLE) {   // a table over the STRING dictionary, indexed by a code (ensure_dict_tables)
-      auto it = p->dict_tables.tables.find(ssgpu_plan::DictTables::key(jg));
-      P->join_cols[g].data = it != p->dict_tables.tables.end() ? it->second.p : nullptr; P->join_cols[g].is_null = nullptr;
-      if (jg.fn == DICT_FN_PARSE) {   // PARSE_STRING: the slot's NULL mask is the failure table (GATHER_NULL of ParseStringNulling)
-        auto f = p->dict_tables.failed.find(ssgpu_plan::DictTables::key(jg));
-        if (f != p->dict_tables.failed.end()) P->join_cols[g].is_null = f->second.as<const uint8_t>();
-      }
+      p->dict_tables.slot(jg.table, &P->join_cols[g].data, &P->join_cols[g].is_null);
       continue;
     }
     if (jg.rhs_col < 0) {   // the per-key run arrays of a NOT_UNIQUE join, indexed by the probed slot
@@ -4644,211 +4229,12 @@ int ssgpu_plan_set_dict(ssgpu_plan* p, const ssgpu_dict* dict) {
   return SSGPU_OK;
 }
 
-// T[c] = fn(value c) for every value of `d`, on the device (string_fn_kernels.hip) -- the tables a plan gathers LENGTH / STRING_OFFSET
-// from, without a plan.  fn: 400 LENGTH (needle ignored), 476 STRING_OFFSET.  out_host: ssgpu_dict_size(d) entries.
-int ssgpu_dict_eval(ssgpu_ctx* c, const ssgpu_dict* d, int32_t fn, const char* needle, int32_t needle_len, int32_t fold_case, int32_t* out_host) {
-  if (!c) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-  if (!d || (fn != 400 && fn != 476) || needle_len < 0 || (needle_len > 0 && !needle)) { c->err = "ssgpu_dict_eval: a dictionary, fn 400 (LENGTH) or 476 (STRING_OFFSET) and the needle's bytes"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
-  if (c->device < 0) { c->err = "no gfx950 device bound to this context (bind-only context)"; return SSGPU_ERROR_NO_DEVICE; }
-  const int32_t n = ssgpu_dict_size(d);
-  if (n > 0 && !out_host) { c->err = "ssgpu_dict_eval: no result buffer"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  DictDevice D; DevBuf needle_dev, table;
-  struct Events { hipEvent_t e[3] = {nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } events;
-  hipEvent_t* ev = events.e;
-  const bool timed = c->debug_timing != 0;   // development: upload and kernel times on stderr (tools/string_fn_bench.py)
-  if (timed) { for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventCreate(&ev[i])); HIP_TRY(c, hipEventRecord(ev[0], c->stream)); }
-  int rc = dict_upload(c, d, &D);
-  if (rc != SSGPU_OK) return rc;
-  if (timed) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-  rc = dict_table_build(c, D, fn, needle, (uint32_t)needle_len, fold_case != 0, &needle_dev, &table);
-  if (rc != SSGPU_OK) return rc;
-  if (timed) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
-  if (n > 0) HIP_TRY(c, hipMemcpyAsync(out_host, table.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (timed) {
-    float up = 0, k = 0;
-    (void)hipEventElapsedTime(&up, ev[0], ev[1]); (void)hipEventElapsedTime(&k, ev[1], ev[2]);
-    fprintf(stderr, "[ssgpu dict_eval] values %d upload_ms %.4f kernel_ms %.4f\n", n, up, k);
-  }
-  return SSGPU_OK;
-}
-// The PARSE_STRING tables of `d` without a plan (string_parse_kernels.hip + the host's strtof / strtod for what the device leaves):
-// out_values_host: ssgpu_dict_size(d) entries of to_type's width, out_failed_host: one byte per value, *out_host_resolved: how many
-// entries the host finished.
-int ssgpu_dict_parse(ssgpu_ctx* c, const ssgpu_dict* d, int32_t to_type, void* out_values_host, uint8_t* out_failed_host, int64_t* out_host_resolved) {
-  if (!c) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-  if (!d || !(dtype_is_numeric(to_type) || to_type == SSGPU_BOOL)) {
-    c->err = "ssgpu_dict_parse: a dictionary and a target type of INT32, UINT32, INT64, UINT64, FLOAT, DOUBLE or BOOL";
-    return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-  }
-  if (c->device < 0) { c->err = "no gfx950 device bound to this context (bind-only context)"; return SSGPU_ERROR_NO_DEVICE; }
-  const int32_t n = ssgpu_dict_size(d);
-  if (n > 0 && (!out_values_host || !out_failed_host)) { c->err = "ssgpu_dict_parse: no result buffer"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  DictDevice D; DevBuf values, failed;
-  struct Events { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } events;
-  hipEvent_t* ev = events.e;
-  const bool timed = c->debug_timing != 0;   // development: upload, kernel and host-share times on stderr (tools/string_parse_bench.py)
-  if (timed) { for (int i = 0; i < 4; ++i) HIP_TRY(c, hipEventCreate(&ev[i])); HIP_TRY(c, hipEventRecord(ev[0], c->stream)); }
-  int rc = dict_upload(c, d, &D);
-  if (rc != SSGPU_OK) return rc;
-  if (timed) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-  int64_t resolved = 0;
-  rc = dict_parse_build(c, D, d, to_type, &values, &failed, &resolved, timed ? ev[3] : nullptr);
-  if (rc != SSGPU_OK) return rc;
-  if (timed) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
-  if (n > 0) {
-    HIP_TRY(c, hipMemcpyAsync(out_values_host, values.p, (size_t)n * (size_t)dtype_width(to_type), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out_failed_host, failed.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (out_host_resolved) *out_host_resolved = resolved;
-  if (timed) {
-    float up = 0, k = 0, h = 0;
-    (void)hipEventElapsedTime(&up, ev[0], ev[1]); (void)hipEventElapsedTime(&k, ev[1], ev[3]); (void)hipEventElapsedTime(&h, ev[3], ev[2]);
-    // host_ms: a floating target's read-back of the failure bytes, the host's strtof / strtod and the patched tables' way back
-    fprintf(stderr, "[ssgpu dict_parse] values %d upload_ms %.4f kernel_ms %.4f host_ms %.4f host_resolved %lld\n", n, up, k, h, (long long)resolved);
-  }
-  return SSGPU_OK;
-}
 int32_t ssgpu_plan_string_steps(const ssgpu_plan* p, ssgpu_string_step* out, int32_t cap) {
   if (!p) return 0;
   std::vector<ssgpu_string_step> steps;
   plan_string_steps(p, &steps);
   for (size_t i = 0; out && i < steps.size() && (int64_t)i < (int64_t)cap; ++i) out[i] = steps[i];
   return (int32_t)steps.size();
-}
-
-// The closed dictionary (ssgpu.h): D_k = D_(k-1) U f_k(D_(k-1)), one step after the other on the device.  A step's domain is D_(k-1)'s
-// values followed by their images -- one (lengths, heap) pair of 2n rows: the length pass (string_map_kernels.hip), the scan, D_(k-1)'s
-// bytes copied to the front of the domain's heap and the write pass behind them -- and goes through the block encoder's chain
-// (encode_domain): the sorted distinct values are D_k, packed on the device as the next step's input, the first n codes are the
-// step's remap (D_(k-1) code -> D_k code) and the second n its table in D_k codes.  After the last step the compose kernel carries
-// every (remap, table) pair through the later remaps into D_final's codes, last step first; what it leaves for step 1 is base's remap.
-int ssgpu_dict_close(ssgpu_ctx* c, const ssgpu_dict* base, const ssgpu_string_step* steps, int32_t n_steps, ssgpu_dict** out, int32_t* remap) {
-  if (!c) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-  if (c->device < 0) { c->err = "no gfx950 device bound to this context (bind-only context)"; return SSGPU_ERROR_NO_DEVICE; }
-  const uint64_t n0 = base ? (uint64_t)ssgpu_dict_size(base) : 0;
-  if (!base || !out || n_steps < 0 || (n_steps > 0 && !steps) || (n0 > 0 && !remap)) { c->err = "ssgpu_dict_close: a dictionary, its steps, and room for the dictionary and the remap"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
-  for (int32_t k = 0; k < n_steps; ++k) {
-    const int fn = steps[k].fn;
-    if (!is_string_producer(fn) && fn != 420) { c->err = "ssgpu_dict_close: step " + std::to_string(k) + " is no string-producing function (404 / 408 / 412 / 416 / 420 / 427 / 480)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
-  }
-  // STRING_REPLACE: a step's pos / len are the codes of its needle / substitute in `base` -- constants of the plan, so values of D_0 -- and
-  // are resolved to bytes once, here; the closed dictionary remembers the step with the two codes in ITS codes (below)
-  std::vector<std::pair<std::string, std::string>> replace_bytes((size_t)n_steps);
-  for (int32_t k = 0; k < n_steps; ++k) {
-    if (steps[k].fn != 480) continue;
-    const char* nb = nullptr; const char* sb = nullptr; int32_t nl = 0, sl = 0;
-    if (steps[k].pos < 0 || steps[k].pos >= (int64_t)n0 || steps[k].len < 0 || steps[k].len >= (int64_t)n0 ||
-        ssgpu_dict_decode(base, (int32_t)steps[k].pos, &nb, &nl) != SSGPU_OK || ssgpu_dict_decode(base, (int32_t)steps[k].len, &sb, &sl) != SSGPU_OK) {
-      c->err = "ssgpu_dict_close: step " + std::to_string(k) + " (STRING_REPLACE): needle code " + std::to_string(steps[k].pos) + " / substitute code " +
-               std::to_string(steps[k].len) + " outside the base dictionary of " + std::to_string(n0) + " values";
-      return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
-    }
-    replace_bytes[(size_t)k] = {std::string(nb, (size_t)nl), std::string(sb, (size_t)sl)};
-  }
-  if (n_steps == 0) return ssgpu_dict_extend(base, nullptr, nullptr, 0, out, remap);
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const bool timed = c->debug_timing != 0;   // development: where a step's time goes, on stderr (tools/string_map_bench.py)
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-  DictDevice cur[2];
-  int rc = dict_upload(c, base, &cur[0]);
-  if (rc != SSGPU_OK) return rc;
-  std::deque<DevBuf> codes;              // per step: 2 x n_(k-1) codes of D_k
-  std::vector<uint64_t> n_in(1, n0);     // n_in[k] = |D_k|
-  std::vector<uint64_t> off_h;
-  std::vector<char> heap_h;
-  for (int32_t k = 0; k < n_steps; ++k) {
-    const DictDevice& in = cur[k & 1];
-    DictDevice& next = cur[(k + 1) & 1];
-    const uint64_t n = in.n;
-    if (2 * n > (uint64_t)kMaxStringDomain) { c->err = "ssgpu_dict_close: more than 2^29 values in a step's dictionary"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
-    codes.emplace_back();
-    DevBuf& kc = codes.back();
-    DevBuf lens, src, dheap, dnull, partials;
-    HIP_TRY(c, kc.ensure(std::max<uint64_t>(2 * n, 1) * 4));
-    HIP_TRY(c, lens.ensure((2 * n + 1) * 8));
-    HIP_TRY(c, src.ensure(std::max<uint64_t>(n, 1) * 8));
-    HIP_TRY(c, dnull.ensure(std::max<uint64_t>(2 * n, 1)));
-    HIP_TRY(c, partials.ensure(ssgpu_str_scan_partials(2 * n) * 8));
-    const auto t0 = now();
-    const int fn = steps[k].fn;
-    const std::string& needle = replace_bytes[(size_t)k].first;
-    const std::string& sub = replace_bytes[(size_t)k].second;
-    DevBuf needle_dev, sub_dev;
-    if (fn == 480) {
-      HIP_TRY(c, needle_dev.ensure(std::max<size_t>(needle.size(), 1))); HIP_TRY(c, sub_dev.ensure(std::max<size_t>(sub.size(), 1)));
-      if (!needle.empty()) HIP_TRY(c, hipMemcpyAsync(needle_dev.p, needle.data(), needle.size(), hipMemcpyHostToDevice, s));
-      if (!sub.empty()) HIP_TRY(c, hipMemcpyAsync(sub_dev.p, sub.data(), sub.size(), hipMemcpyHostToDevice, s));
-      HIP_TRY(c, ssgpu_launch_str_replace_len(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), n, needle_dev.as<const uint8_t>(), (uint32_t)needle.size(),
-                                              (uint32_t)sub.size(), lens.as<uint64_t>(), s));
-    } else {
-      HIP_TRY(c, ssgpu_launch_str_map_len(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), n, fn, steps[k].has_len ? 1 : 0, steps[k].pos, steps[k].len,
-                                          lens.as<uint64_t>(), src.as<uint64_t>(), s));
-    }
-    HIP_TRY(c, ssgpu_launch_str_scan(lens.as<uint64_t>(), 2 * n, partials.as<uint64_t>(), s));
-    uint64_t ends[2] = {0, 0};             // the domain's heap: D_(k-1)'s bytes end at ends[0], the images at ends[1]
-    HIP_TRY(c, hipMemcpyAsync(&ends[0], lens.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&ends[1], lens.as<uint64_t>() + 2 * n, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, dheap.ensure(ends[1] + 8));
-    if (ends[0]) HIP_TRY(c, hipMemcpyAsync(dheap.p, in.heap.p, ends[0], hipMemcpyDeviceToDevice, s));
-    if (fn == 480)
-      HIP_TRY(c, ssgpu_launch_str_replace_write(in.heap.as<const uint8_t>(), in.offs.as<const uint64_t>(), lens.as<const uint64_t>() + n, n, needle_dev.as<const uint8_t>(),
-                                                (uint32_t)needle.size(), sub_dev.as<const uint8_t>(), (uint32_t)sub.size(), dheap.as<uint8_t>(), s));
-    else
-      HIP_TRY(c, ssgpu_launch_str_map_write(in.heap.as<const uint8_t>(), src.as<const uint64_t>(), lens.as<const uint64_t>() + n, n, fn == 416 ? 1 : fn == 420 ? 2 : 0,
-                                            dheap.as<uint8_t>(), s));
-    HIP_TRY(c, hipMemsetAsync(dnull.p, 0, std::max<uint64_t>(2 * n, 1), s));
-    if (timed) HIP_TRY(c, hipStreamSynchronize(s));
-    const auto t1 = now();
-    uint32_t D = 0;
-    rc = encode_domain(c, s, dheap.as<uint8_t>(), lens.as<uint64_t>(), true, dnull.as<uint8_t>(), 2 * n, {{kc.as<int32_t>(), 0, 2 * n}}, STRFN_HEAP_PAD, &off_h, &heap_h, &D,
-                       next.offs, next.heap);
-    if (rc != SSGPU_OK) return rc;
-    if (n == 0) {   // an empty dictionary stays empty: give the next step the packed form of nothing
-      HIP_TRY(c, next.offs.ensure(8)); HIP_TRY(c, next.heap.ensure(STRFN_HEAP_PAD));
-      HIP_TRY(c, hipMemsetAsync(next.offs.p, 0, 8, s)); HIP_TRY(c, hipMemsetAsync(next.heap.p, 0, STRFN_HEAP_PAD, s));
-      HIP_TRY(c, hipStreamSynchronize(s));
-    }
-    next.n = D;
-    n_in.push_back(D);
-    if (timed) fprintf(stderr, "[ssgpu dict_close] step %d fn %d values %llu -> %u map_ms %.4f encode_ms %.4f\n", k, fn, (unsigned long long)n, D, ms(t0, t1), ms(t1, now()));
-  }
-  // compose, last step first: `later` maps D_k's codes to D_final's (nothing for the last step); the step leaves D_(k-1)'s in `to_final`
-  const uint64_t n_final = n_in[(size_t)n_steps];
-  DevBuf tables, to_final[2];
-  HIP_TRY(c, tables.ensure(std::max<uint64_t>(n_final * (uint64_t)n_steps, 1) * 4));
-  HIP_TRY(c, hipMemsetAsync(tables.p, 0, std::max<uint64_t>(n_final * (uint64_t)n_steps, 1) * 4, s));
-  const auto t2 = now();
-  for (int32_t k = n_steps - 1; k >= 0; --k) {
-    const uint64_t n = n_in[(size_t)k];
-    DevBuf& mine = to_final[k & 1];
-    HIP_TRY(c, mine.ensure(std::max<uint64_t>(n, 1) * 4));
-    const int32_t* later = k == n_steps - 1 ? nullptr : to_final[(k + 1) & 1].as<int32_t>();
-    HIP_TRY(c, ssgpu_launch_str_map_compose(codes[(size_t)k].as<int32_t>(), n, later, n_in[(size_t)k + 1], n_final, mine.as<int32_t>(),
-                                            tables.as<int32_t>() + (uint64_t)k * n_final, s));
-  }
-  std::vector<int32_t> tables_h((size_t)(n_final * (uint64_t)n_steps));
-  if (!tables_h.empty()) HIP_TRY(c, hipMemcpyAsync(tables_h.data(), tables.p, tables_h.size() * 4, hipMemcpyDeviceToHost, s));
-  if (n0) HIP_TRY(c, hipMemcpyAsync(remap, to_final[0].p, n0 * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  if (timed) fprintf(stderr, "[ssgpu dict_close] compose_ms %.4f\n", ms(t2, now()));
-  // (off_h / heap_h: the last step's distinct values, as the encoder copied them back)
-  ssgpu_dict* d = nullptr;
-  rc = ssgpu_dict_create_sorted(heap_h.data(), off_h.data(), (int64_t)n_final, &d);
-  if (rc != SSGPU_OK) { c->err = "ssgpu_dict_close: too many distinct values"; return rc; }
-  // a STRING_REPLACE step is remembered with its two constants as codes of THIS dictionary: the plan created anew over it bakes them so
-  std::vector<ssgpu_string_step> kept(steps, steps + n_steps);
-  for (ssgpu_string_step& st : kept)
-    if (st.fn == 480) { st.has_len = 0; st.pos = remap[st.pos]; st.len = remap[st.len]; }
-  ssgpu_dict_set_steps(d, kept.data(), n_steps, tables_h.data());
-  *out = d;
-  return SSGPU_OK;
 }
 
 const ssgpu_dict* ssgpu_result_column_dict(ssgpu_result* r, int32_t i) {

@@ -180,7 +180,7 @@ int ssgpu_dict_extend(const ssgpu_dict* base, const char* const* strings, const 
   return SSGPU_OK;
 }
 
-// internal (runtime.cpp): a dictionary over values that are already sorted and unique -- the distinct strings of a device
+// internal (runtime.cpp, string_dict.cpp): a dictionary over values that are already sorted and unique -- the distinct strings of a device
 // block in code order, `offsets[n + 1]` into `heap` -- taken as they are
 int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offsets, int64_t n, ssgpu_dict** out) {
   if (!out || n < 0 || n > (int64_t)std::numeric_limits<int32_t>::max()) return SSGPU_ERROR_INVALID_ARGUMENT_VALUE;
@@ -191,7 +191,7 @@ int ssgpu_dict_create_sorted(const char* heap, const uint64_t* offsets, int64_t 
   return SSGPU_OK;
 }
 
-// internal (runtime.cpp: ssgpu_dict_close): makes `d` a closed dictionary -- `tables` holds n tables of ssgpu_dict_size(d) entries, one after the other
+// internal (string_dict.cpp: ssgpu_dict_close): makes `d` a closed dictionary -- `tables` holds n tables of ssgpu_dict_size(d) entries, one after the other
 void ssgpu_dict_set_steps(ssgpu_dict* d, const ssgpu_string_step* steps, int32_t n, const int32_t* tables) {
   const size_t size = d->values.size();
   d->steps.assign(steps, steps + n);
@@ -209,7 +209,7 @@ int ssgpu_dict_step_table(const ssgpu_dict* d, int32_t k, int32_t* out_host) {
   return SSGPU_OK;
 }
 
-// internal (runtime.cpp): the dictionary packed for the device -- `offsets[n + 1]` into one byte heap of ssgpu_dict_heap_bytes
+// internal (string_dict.cpp): the dictionary packed for the device -- `offsets[n + 1]` into one byte heap of ssgpu_dict_heap_bytes
 uint64_t ssgpu_dict_heap_bytes(const ssgpu_dict* d) {
   uint64_t total = 0;
   if (d) for (const std::string& v : d->values) total += v.size();

@@ -3,8 +3,8 @@
 // A STRING value in a plan is the INT32 code of the plan's order-preserving dictionary, so f(s) = T[code(s)] with
 // T[c] = f(dictionary[c]).  The kernel below builds T on the device from the packed dictionary (`offsets[n + 1]` into one
 // byte heap); the pipeline reads it per row with GATHER_32 (vm_body.inc).  Functions (reference OperatorIds):
-//   LENGTH (400)         T[c] = byte length                                  (string_evaluators.h Length)
-//   STRING_OFFSET (476)  T[c] = 1-based byte position of the FIRST occurrence of the needle, 0 when absent; an empty
+//   OP_LENGTH            T[c] = byte length                                  (string_evaluators.h Length)
+//   OP_STRING_OFFSET     T[c] = 1-based byte position of the FIRST occurrence of the needle, 0 when absent; an empty
 //                        needle is found at 1 (string_evaluators.h:69-73: haystack.find(needle) + 1)
 // `fold` compares through ascii_tolower on both sides (the TO_LOWER(haystack), TO_LOWER(needle) form StringContainsCI
 // binds, string_bound_expressions.cc:193-205): only A-Z fold, bytes >= 0x80 are left alone.
@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "launch.h"
+#include "opids.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(STRFN_THREADS) void ssgpu_str_fn_kernel(const u8* _
   const u32 lane = threadIdx.x & 63;
   const bool live = row < n;
   const u64 off = live ? offs[row] : 0, len = live ? offs[row + 1] - off : 0;
-  if (fn == 400) { if (live) T[row] = (u32)len; return; }
+  if (fn == OP_LENGTH) { if (live) T[row] = (u32)len; return; }
   const bool fold = fold_i != 0;
   if (nlen == 0) { if (live) T[row] = 1u; return; }               // "".find("") == 0
   const u32 n0 = strfn_byte(needle[0], fold);

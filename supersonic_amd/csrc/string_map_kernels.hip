@@ -2,13 +2,13 @@
 //
 // A STRING value in a plan is a code of the plan's one dictionary, so a function whose result is a STRING is a table
 // T[code(s)] = code(f(s)) too -- once the dictionary holds every image (the CLOSED dictionary, ssgpu.h).  One closing step takes
-// the packed dictionary D (`offsets[n + 1]` into one byte heap, the form runtime.cpp: dict_upload makes) and builds the string
+// the packed dictionary D (`offsets[n + 1]` into one byte heap, the form string_dict.cpp: dict_upload makes) and builds the string
 // domain "D's values followed by their images" -- 2n rows -- which then goes through the encoder of string_dict_kernels.hip:
 //   length pass -- ssgpu_str_map_len_kernel: lens[i] = |v_i|, lens[n + i] = |f(v_i)|, src[i] = where the image's bytes start in
 //                  D's heap.  Every function here maps a value to a SLICE of it, byte-transformed or not:
-//                    LTRIM 404 / RTRIM 408 / TRIM 412   strip byte 0x20 only (string_evaluators.h:96-120)
-//                    TO_UPPER 416 (TO_LOWER 420)        the whole value, folded on the way out (:122-146)
-//                    SUBSTRING 427                      substr(pos', len) with the evaluator's position rule (:41-67)
+//                    OP_LTRIM / OP_RTRIM / OP_TRIM      strip byte 0x20 only (string_evaluators.h:96-120)
+//                    OP_TOUPPER (OP_TOLOWER)            the whole value, folded on the way out (:122-146)
+//                    OP_SUBSTRING                       substr(pos', len) with the evaluator's position rule (:41-67)
 //                  so the length pass of SUBSTRING and the folds reads no byte at all, and the trims read the two ends only;
 //   scan        -- string_dict_kernels.hip (the caller);
 //   write pass  -- ssgpu_str_map_write_kernel: the image's bytes into the domain's heap behind D's own bytes, folded
@@ -17,14 +17,15 @@
 // the heap is read in ALIGNED 8-byte (lane form) / 16-byte (wave form) words -- its allocation extends STRFN_HEAP_PAD bytes
 // past the last value and starts 16-byte aligned.  A long value's first and last non-space byte are found by the wave, 1 KiB
 // per step from either end, with a minimum / maximum over the lanes; the loop stops at the first step that has one.
-// STRING_REPLACE 480 is NOT a slice -- it searches the whole value, its image may be longer than the value and its bytes come from two
+// OP_STRING_REPLACE is NOT a slice -- it searches the whole value, its image may be longer than the value and its bytes come from two
 // places -- and has a length and a write pass of its own, ssgpu_str_replace_len_kernel / _write_kernel, further down.
 //
 // ssgpu_str_map_compose_kernel: after the last step, a step's (remap, table) pair -- codes of ITS dictionary D_k -- carried
-// through the later steps' remaps into codes of the final dictionary (runtime.cpp: ssgpu_dict_close).
+// through the later steps' remaps into codes of the final dictionary (string_dict.cpp: ssgpu_dict_close).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "launch.h"
+#include "opids.h"
 
 typedef unsigned long long u64;
 typedef long long i64;
@@ -125,9 +126,9 @@ __global__ __launch_bounds__(STRMAP_THREADS) void ssgpu_str_map_len_kernel(const
   const u32 lane = threadIdx.x & 63;
   const bool live = row < n;
   const u64 off = live ? offs[row] : 0, len = live ? offs[row + 1] - off : 0;
-  const bool trims = fn == 404 || fn == 408 || fn == 412;
+  const bool trims = fn == OP_LTRIM || fn == OP_RTRIM || fn == OP_TRIM;
   u64 lo = off, hi = off + len;                      // the image is heap[lo, hi)
-  if (fn == 427) {
+  if (fn == OP_SUBSTRING) {
     // SubstringTernary / SubstringBinary: a position > 0 counts from 1, one <= 0 from the end and is clamped at 0; StringPiece::substr clamps both
     i64 p = pos;
     if (p > 0) p -= 1; else { p += (i64)len; if (p < 0) p = 0; }
@@ -136,8 +137,8 @@ __global__ __launch_bounds__(STRMAP_THREADS) void ssgpu_str_map_len_kernel(const
     const u64 want = has_len ? (sublen > 0 ? (u64)sublen : 0) : room;
     lo = off + start; hi = lo + (want < room ? want : room);
   } else if (trims && live && len <= STRMAP_LONG) {
-    if (fn != 408) lo = strmap_first_nonspace(heap, off, off + len);
-    if (fn != 404) hi = strmap_last_nonspace(heap, lo, off + len);
+    if (fn != OP_RTRIM) lo = strmap_first_nonspace(heap, off, off + len);
+    if (fn != OP_LTRIM) hi = strmap_last_nonspace(heap, lo, off + len);
   }
   if (trims) {
     u64 todo = __ballot(live && len > STRMAP_LONG);
@@ -146,8 +147,8 @@ __global__ __launch_bounds__(STRMAP_THREADS) void ssgpu_str_map_len_kernel(const
       todo &= todo - 1;
       const u64 o = __shfl(off, who, 64), l = __shfl(len, who, 64);
       u64 a = o, b = o + l;
-      if (fn != 408) a = strmap_wave_first_nonspace(heap, o, o + l, lane);
-      if (fn != 404) b = strmap_wave_last_nonspace(heap, a, o + l, lane);
+      if (fn != OP_RTRIM) a = strmap_wave_first_nonspace(heap, o, o + l, lane);
+      if (fn != OP_LTRIM) b = strmap_wave_last_nonspace(heap, a, o + l, lane);
       if ((int)lane == who) { lo = a; hi = b; }
     }
   }
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(STRMAP_THREADS) void ssgpu_str_map_write_kernel(con
   }
 }
 
-// ---- STRING_REPLACE 480 (string_evaluators.h:76-90 -> utils/strings/util.cc:201-222, replace_all): the first producer whose image is
+// ---- OP_STRING_REPLACE (string_evaluators.h:76-90 -> utils/strings/util.cc:201-222, replace_all): the first producer whose image is
 // no slice of its value.  Matches are leftmost and non-overlapping, found left to right (pos = find(needle, start); start = pos +
 // |needle|), the substitute is never searched again, bytes are bytes, and an empty needle leaves the value as it is.  Both passes make
 // the same SELECTION of matches and differ in what they do with it:

@@ -1,4 +1,4 @@
-// string_parse_kernels.hip -- PARSE_STRING (ParseStringQuiet 437 / ParseStringNulling 438): a STRING value turned into a number,
+// string_parse_kernels.hip -- PARSE_STRING (OP_PARSE_STRING_QUIET / OP_PARSE_STRING_NULLING): a STRING value turned into a number,
 // once per DISTINCT value.
 //
 // Like string_fn_kernels.hip: a STRING value in a plan is the code of the plan's dictionary, so parse(s) = V[code(s)] and
@@ -22,7 +22,7 @@
 //       w <= 2^24, |e| <= 10.  There w and 10^|e| are exact, so ONE correctly rounded multiply or divide is the correctly rounded
 //       result (Clinger); the sign goes on last ("-0" is -0.0); a FLOAT never goes through a double.  Every other value but the
 //       empty one (a failure with value 0: no parser is asked) is marked STRPARSE_HARD in F and left to the host, which calls
-//       strtod / strtof on the value's own bytes and patches both tables (runtime.cpp).  The device never decides that a floating
+//       strtod / strtof on the value's own bytes and patches both tables (string_dict.cpp).  The device never decides that a floating
 //       parse FAILED.
 //
 // Work split as in string_fn_kernels.hip: one lane per value of up to STRPARSE_LONG = 128 bytes, a whole wave per longer value
