@@ -144,8 +144,10 @@ enum {
   SSGPU_ERROR_ATTRIBUTE_MISSING = 403,
   SSGPU_ERROR_ATTRIBUTE_EXISTS = 404,
   SSGPU_ERROR_INVALID_ARGUMENT_TYPE = 405,
+  SSGPU_ERROR_ATTRIBUTE_IS_NULLABLE = 406,   /* the key of a FOREIGN_FILTER / ROWID_MERGE_JOIN is a NULLABLE attribute */
   SSGPU_ERROR_INVALID_ARGUMENT_VALUE = 407,
   SSGPU_ERROR_ATTRIBUTE_AMBIGUOUS = 408,
+  SSGPU_ERROR_FOREIGN_KEY_INVALID = 501,     /* ROWID_MERGE_JOIN: a selected left row's key is no row of the right table */
   SSGPU_INTERRUPTED = 1000,
   /* not a reference code: no gfx950 device / HIP runtime failure */
   SSGPU_ERROR_NO_DEVICE = 2000,
@@ -248,7 +250,7 @@ enum {
   SSGPU_OP_BEST_EFFORT_GROUP_AGGREGATE = 10, /* BestEffortGroupAggregate(keys, spec, opts, child) aggregate.h:246-250; option0 =
                                       GroupAggregateOptions::memory_quota in bytes (0 = none): the result block holds quota / bytes of a
                                       result row groups; run with ssgpu_plan_run_best_effort (ABI 9) */
-  SSGPU_OP_HASH_JOIN = 9           /* HashJoinOperation(type, lhs keys, rhs keys, result projector,
+  SSGPU_OP_HASH_JOIN = 9,          /* HashJoinOperation(type, lhs keys, rhs keys, result projector,
                                       uniqueness, lhs, rhs) hash_join.h:37-56.  `child` = lhs chain,
                                       `child2` = the rhs op, which must be a SCAN of the auxiliary
                                       input (a device-resident table).  UNIQUE rhs keys: the probe
@@ -256,6 +258,39 @@ enum {
                                       pipeline (a repeated key is reported at run time); NOT_UNIQUE:
                                       rows multiply -- the lhs pipeline materialises its side and an
                                       expand stage emits one row per match (lhs order, rhs order) */
+  /* The structured-filter joins (cursor/core/foreign_filter.h:25-47, rowid_merge_join.h:29-41): a parent table is filtered
+   * first; FOREIGN_FILTER then keeps the child rows whose foreign key survived and renumbers the key, after which a foreign
+   * key IS the parent's row number and ROWID_MERGE_JOIN fetches the parent's columns by it.  Both take the plan shape of
+   * HASH_JOIN -- `child` = the input (left) chain, `child2` = a SCAN of the auxiliary input -- and are fused into the input's
+   * pipeline like its UNIQUE INNER form: Filters below, and whatever follows above, share the kernel.  Neither builds or
+   * allocates an index.
+   *
+   * FOREIGN_FILTER: ForeignFilter(filter_key, foreign_key, filter, input).  `proj` = foreign_key (over the input), `proj2` =
+   *   filter_key (over the auxiliary input, the filter).  Each must select exactly ONE attribute (else
+   *   ERROR_ATTRIBUTE_COUNT_MISMATCH) of type INT64 (else ERROR_ATTRIBUTE_TYPE_MISMATCH) that is NOT_NULLABLE (else
+   *   ERROR_ATTRIBUTE_IS_NULLABLE) -- the filter key is checked first (foreign_filter.cc:188-244).  The result has the input's
+   *   schema in the input's column order; the foreign-key column keeps its name and is INT64 NOT_NULLABLE.  Its rows are the
+   *   input rows whose key equals some filter_key[j], in input order, the key replaced by j (a search of the sorted filter
+   *   column per row); every other column is copied bit for bit, NULL masks and STRING codes included.
+   *   The filter keys must be STRICTLY ASCENDING as signed 64-bit values (the reference: "unique and ascending").  The device
+   *   verifies that at the start of every run, after the auxiliary input was bound; a table that is not fails the run with
+   *   ERROR_INVALID_ARGUMENT_VALUE and nothing is searched.  The INPUT's keys need not be ascending: the reference merges two
+   *   ascending streams and requires it, this implementation searches per row and its result does not depend on the order.
+   * ROWID_MERGE_JOIN: RowidMergeJoin(left_key_selector, result_projector, left, right).  `proj` = the left key (same three
+   *   checks, rowid_merge_join.cc:186-211), `proj3` = the result projector, bound exactly as HASH_JOIN's (entries tagged with
+   *   `source`: 0 = left, 1 = right).  Every selected left row gives one result row whose right columns come from right row
+   *   `key`.  A selected row with key < 0 or key >= the right row count fails the run with ERROR_FOREIGN_KEY_INVALID ("No
+   *   parent record with ID > <right row count>", rowid_merge_join.cc:99-102); the key is compared as the signed 64-bit value
+   *   it is, before it is narrowed to a row number (2^32 against a 3-row table is an error, not row 0), and such a row gathers
+   *   nothing, so a failing run reads inside the table too.  Rows that a Filter below has dropped are not checked.  The run
+   *   fails as a whole, like signaling division: the reference's "rows before the failure" are not served.  The left keys need
+   *   not be ascending either.
+   * Restrictions, as HASH_JOIN's: the auxiliary side is a ScanView of a table (anything else: ERROR_NOT_IMPLEMENTED); a plan has
+   * ONE auxiliary table, so a FOREIGN_FILTER feeding a ROWID_MERGE_JOIN is two plans, the second scanning the first's device
+   * result; the auxiliary row count stays below 2^32 - 1 (ssgpu_plan_set_aux_input).  Chunked staging takes both as row-local
+   * operations. */
+  SSGPU_OP_FOREIGN_FILTER = 11,
+  SSGPU_OP_ROWID_MERGE_JOIN = 12
 };
 enum { SSGPU_JOIN_INNER = 0, SSGPU_JOIN_LEFT_OUTER = 1 };           /* JoinType, supersonic.proto:108-113 */
 enum { SSGPU_KEYS_NOT_UNIQUE = 0, SSGPU_KEYS_UNIQUE = 1 };            /* KeyUniqueness, :115-118 */
@@ -269,16 +304,17 @@ typedef struct ssgpu_op {
   int32_t agg_n;
   int32_t sort_first;
   int32_t sort_n;
-  int32_t child2;     /* HASH_JOIN: index of the rhs op (must precede); else unused */
+  int32_t child2;     /* HASH_JOIN / FOREIGN_FILTER / ROWID_MERGE_JOIN: index of the rhs (filter, right) op (must precede); else unused */
   int64_t option0;    /* GROUP: max_unique_keys_in_result (0 = no limit, n > 0 = limit n, -1 = limit 0; aggregate.h:160-205);
                          DISTINCT aggregates under it keep ONE seen-value set per result row, the folded last row included
                          (column_aggregator.cc:308-376), and CONCAT joins a result row's values in input order over all its keys;
                          SORT: memory limit (ignored: no spill path);
                          SCAN: input index (0 = the plan input, 1 = the auxiliary input);
                          HASH_JOIN: JoinType | KeyUniqueness << 8             */
-  int32_t proj2_first; /* HASH_JOIN: rhs key selector (proj_first/proj_n = lhs key selector) */
+  int32_t proj2_first; /* HASH_JOIN: rhs key selector (proj_first/proj_n = lhs key selector); FOREIGN_FILTER: the filter key
+                          (proj_first/proj_n = the input's foreign key); ROWID_MERGE_JOIN: unused (proj_first/proj_n = the left key) */
   int32_t proj2_n;
-  int32_t proj3_first; /* HASH_JOIN: result projector (entries tagged with `source`) */
+  int32_t proj3_first; /* HASH_JOIN / ROWID_MERGE_JOIN: result projector (entries tagged with `source`) */
   int32_t proj3_n;
 } ssgpu_op;
 
@@ -759,7 +795,7 @@ int ssgpu_plan_run_block(ssgpu_plan* plan, const ssgpu_block* block, ssgpu_resul
  * (ssgpu_ctx_synchronize, or fetching the result).
  * Which plans (ABI 10; ssgpu_plan_chunked_form tells, also on a bind-only context):
  *   1  ONE ScalarAggregate stage (over Filter / Compute / Project) -- the path's headline shape: the state fold described above;
- *   2  plans of row-local operations only (Filter / Compute / Project / HashJoin against the auxiliary input; filter.cc:96-128 pulls
+ *   2  plans of row-local operations only (Filter / Compute / Project / HashJoin, ForeignFilter, RowidMergeJoin against the auxiliary input; filter.cc:96-128 pulls
  *      its child the same way): every chunk runs the plan, its result rows are appended on the device; the rows keep the input's order;
  *   3  plans whose first blocking operation on the input's path is a GroupAggregate without a key limit, over row-local operations
  *      (aggregate_groups.cc:212-282 ProcessInput): every chunk runs the plan UP TO AND INCLUDING the GroupAggregate -- in whatever

@@ -124,7 +124,8 @@ enum ReturnCode {
   OK = 0, ERROR_UNKNOWN_ERROR = 100, ERROR_GENERAL_IO_ERROR = 101, ERROR_MEMORY_EXCEEDED = 102, ERROR_NOT_IMPLEMENTED = 103,
   ERROR_EVALUATION_ERROR = 104, ERROR_TOO_MANY_ROWS = 302, ERROR_ATTRIBUTE_COUNT_MISMATCH = 401,
   ERROR_ATTRIBUTE_TYPE_MISMATCH = 402, ERROR_ATTRIBUTE_MISSING = 403, ERROR_ATTRIBUTE_EXISTS = 404,
-  ERROR_INVALID_ARGUMENT_TYPE = 405, ERROR_INVALID_ARGUMENT_VALUE = 407, INTERRUPTED = 1000
+  ERROR_INVALID_ARGUMENT_TYPE = 405, ERROR_ATTRIBUTE_IS_NULLABLE = 406, ERROR_INVALID_ARGUMENT_VALUE = 407,
+  ERROR_FOREIGN_KEY_INVALID = 501, INTERRUPTED = 1000
 };
 
 // ---- errors (base/exception/exception.h:53, result.h:43-130) ----------------------------
@@ -791,8 +792,8 @@ inline const View& SucceedOrDie(ResultView result_view) {   // cursor.h:124-127
 }
 
 // cursor/proto/cursors.proto:13-67 (the ids of the cursors this path has)
-enum CursorId { FILE_INPUT = 3, VIEW = 7, AGGREGATE_CLUSTERS = 8, BEST_EFFORT_GROUP_AGGREGATE = 10, COMPUTE = 15, FILTER = 16, GROUP_AGGREGATE = 18, HASH_JOIN = 19, PROJECT = 26,
-                SCALAR_AGGREGATE = 29, SORT = 30, UNKNOWN_ID = 42 };
+enum CursorId { FILE_INPUT = 3, VIEW = 7, AGGREGATE_CLUSTERS = 8, BEST_EFFORT_GROUP_AGGREGATE = 10, COMPUTE = 15, FILTER = 16, FOREIGN_FILTER = 17, GROUP_AGGREGATE = 18, HASH_JOIN = 19, PROJECT = 26,
+                ROWID_MERGE_JOIN = 28, SCALAR_AGGREGATE = 29, SORT = 30, UNKNOWN_ID = 42 };
 class CursorTransformer;
 
 class Operation;
@@ -1461,7 +1462,54 @@ class HashJoinOp : public BasicOperation {
   std::unique_ptr<const MultiSourceProjector> rp_;
   std::unique_ptr<Operation> lhs_, rhs_;
 };
+// ForeignFilter (cursor/core/foreign_filter.h:25-47) and RowidMergeJoin (rowid_merge_join.h:29-41): `input` is the pipeline, `aux`
+// = ScanView(table) the resident filter / right table.  key = the input-side key; aux_key = the filter key (ForeignFilter only);
+// result = the two-source result projector (RowidMergeJoin only).
+class StructuredJoinOp : public BasicOperation {
+ public:
+  StructuredJoinOp(int kind, const SingleSourceProjector* key, const SingleSourceProjector* aux_key, const MultiSourceProjector* result,
+                   Operation* input, Operation* aux) : kind_(kind), key_(key), aux_key_(aux_key), result_(result), input_(input), aux_(aux) {}
+  // the reference's child order: ForeignFilter(filter, input), RowidMergeJoin(left, right)
+  std::vector<Operation*> children() const override {
+    std::vector<Operation*> c;
+    if (kind_ == SSGPU_OP_FOREIGN_FILTER) { c.push_back(aux_.get()); c.push_back(input_.get()); } else { c.push_back(input_.get()); c.push_back(aux_.get()); }
+    return c;
+  }
+  const char* name() const override { return kind_ == SSGPU_OP_FOREIGN_FILTER ? "ForeignFilter" : "RowidMergeJoin"; }
+  CursorId cursor_id() const override { return kind_ == SSGPU_OP_FOREIGN_FILTER ? FOREIGN_FILTER : ROWID_MERGE_JOIN; }
+  int Emit(Builder* b) const override {
+    const int l = EmitChild(input_.get(), b);
+    // a plan has ONE auxiliary table (ssgpu.h): a second, different one is refused here, where it can still be told from the first
+    const View* before = b->scan_aux;
+    b->aux = true; const int r = EmitChild(aux_.get(), b); b->aux = false;
+    if (before && b->scan_aux != before && b->error.empty())
+      b->error = std::string(name()) + ": a plan has one auxiliary table, and this plan already joins against another one (run the "
+                 "operations as two plans, the second scanning the first's device result)";
+    ssgpu_op o = Blank(kind_, l);
+    o.child2 = r;
+    b->ProjRange(key_->entries, &o.proj_first, &o.proj_n);
+    if (aux_key_) b->ProjRange(aux_key_->entries, &o.proj2_first, &o.proj2_n);
+    if (result_) b->ProjRange(result_->entries, &o.proj3_first, &o.proj3_n);
+    return b->Op(o);
+  }
+  const BufferAllocator* EffectiveAllocator() const override { return allocator_ ? allocator_ : AllocatorOf(input_.get()); }
+ private:
+  int kind_;
+  std::unique_ptr<const SingleSourceProjector> key_, aux_key_;
+  std::unique_ptr<const MultiSourceProjector> result_;
+  std::unique_ptr<Operation> input_, aux_;
+};
 }  // namespace internal
+
+// Takes ownership of both projectors and both children (foreign_filter.h:41-47).  `filter` must be ScanView(table) with strictly
+// ascending INT64 keys; the input's keys may come in any order.
+inline Operation* ForeignFilter(const SingleSourceProjector* filter_key, const SingleSourceProjector* foreign_key, Operation* filter, Operation* input) {
+  return new internal::StructuredJoinOp(SSGPU_OP_FOREIGN_FILTER, foreign_key, filter_key, nullptr, input, filter);
+}
+// Takes ownership of both projectors and both children (rowid_merge_join.h:35-41).  `right` must be ScanView(table).
+inline Operation* RowidMergeJoin(const SingleSourceProjector* left_key_selector, const MultiSourceProjector* result_projector, Operation* left, Operation* right) {
+  return new internal::StructuredJoinOp(SSGPU_OP_ROWID_MERGE_JOIN, left_key_selector, nullptr, result_projector, left, right);
+}
 
 // Takes ownership of all projectors and both children (hash_join.h:48-56).
 inline Operation* HashJoin(JoinType join_type, const SingleSourceProjector* lhs_key_selector, const SingleSourceProjector* rhs_key_selector,

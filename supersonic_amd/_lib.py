@@ -29,7 +29,9 @@ ERROR_ATTRIBUTE_TYPE_MISMATCH = 402
 ERROR_ATTRIBUTE_MISSING = 403
 ERROR_ATTRIBUTE_EXISTS = 404
 ERROR_INVALID_ARGUMENT_TYPE = 405
+ERROR_ATTRIBUTE_IS_NULLABLE = 406
 ERROR_INVALID_ARGUMENT_VALUE = 407
+ERROR_FOREIGN_KEY_INVALID = 501
 INTERRUPTED = 1000
 ERROR_NO_DEVICE = 2000
 ERROR_HIP = 2001
@@ -42,6 +44,7 @@ KEYS_NOT_UNIQUE, KEYS_UNIQUE = 0, 1
 OP_SCAN, OP_COMPUTE, OP_FILTER, OP_PROJECT, OP_SCALAR_AGGREGATE, OP_GROUP_AGGREGATE, OP_AGGREGATE_CLUSTERS, OP_SORT = 1, 2, 3, 4, 5, 6, 7, 8
 OP_BEST_EFFORT_GROUP_AGGREGATE = 10
 OP_HASH_JOIN = 9
+OP_FOREIGN_FILTER, OP_ROWID_MERGE_JOIN = 11, 12
 
 
 class Attr(C.Structure):

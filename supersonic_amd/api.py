@@ -28,7 +28,8 @@ from ._lib import (INT32, INT64, UINT32, UINT64, FLOAT, DOUBLE, BOOL, DATE, DATE
                    OK, ERROR_UNKNOWN, ERROR_GENERAL_IO_ERROR, ERROR_MEMORY_EXCEEDED, ERROR_NOT_IMPLEMENTED, ERROR_EVALUATION_ERROR,
                    ERROR_TOO_MANY_ROWS, ERROR_ATTRIBUTE_COUNT_MISMATCH, ERROR_ATTRIBUTE_TYPE_MISMATCH,
                    ERROR_ATTRIBUTE_MISSING, ERROR_ATTRIBUTE_EXISTS, ERROR_INVALID_ARGUMENT_TYPE,
-                   ERROR_INVALID_ARGUMENT_VALUE, INTERRUPTED, ERROR_NO_DEVICE, ERROR_HIP)
+                   ERROR_INVALID_ARGUMENT_VALUE, INTERRUPTED, ERROR_NO_DEVICE, ERROR_HIP,
+                   ERROR_ATTRIBUTE_IS_NULLABLE, ERROR_FOREIGN_KEY_INVALID)
 
 kDefaultRowCount = 1024  # Cursor::kDefaultRowCount, cursor/base/cursor.h:133
 
@@ -1139,6 +1140,63 @@ def HashJoin(join_type, lhs_key_selector, rhs_key_selector, result_projector, rh
     return HashJoinOperation(join_type, lhs_key_selector, rhs_key_selector, result_projector, rhs_key_uniqueness, lhs_child, rhs_child)
 
 
+def _emit_aux_side(b, child, what):
+    """The auxiliary side of a ForeignFilter / RowidMergeJoin.  A plan has ONE auxiliary table (include/ssgpu.h): a second, different
+    one is refused here, where it can still be told from the first."""
+    before = b.scan_aux
+    b.aux = True
+    try:
+        r = child._emit(b)
+    finally:
+        b.aux = False
+    if before is not None and b.scan_aux is not before:
+        raise SupersonicException(L.ERROR_NOT_IMPLEMENTED, "%s: a plan has one auxiliary table, and this plan already joins against another "
+                                  "one (run the operations as two plans, the second scanning the first's device result)" % what)
+    return r
+
+
+class ForeignFilterOperation(Operation):
+    """cursor/core/foreign_filter.h:25-47: keeps the input rows whose foreign key is one of the filter's keys and replaces the key
+    by that key's row in the filter.  The filter must be ScanView(table) -- a resident table whose INT64 keys are strictly
+    ascending (verified on the device; ERROR_INVALID_ARGUMENT_VALUE otherwise); the search is fused into the input's pipeline."""
+
+    def __init__(self, filter_key, foreign_key, filter_child, input_child):
+        self.filter_key, self.foreign_key = filter_key, foreign_key
+        self.child, self.rhs_child = input_child, filter_child
+
+    def _emit(self, b):
+        c = self.child._emit(b)
+        r = _emit_aux_side(b, self.rhs_child, "ForeignFilter")
+        pf, pn = b.proj(self.foreign_key)
+        p2f, p2n = b.proj(self.filter_key)
+        return b.op(kind=L.OP_FOREIGN_FILTER, child=c, child2=r, proj_first=pf, proj_n=pn, proj2_first=p2f, proj2_n=p2n)
+
+
+def ForeignFilter(filter_key, foreign_key, filter, input):   # noqa: A002 (the reference's argument names)
+    return ForeignFilterOperation(filter_key, foreign_key, filter, input)
+
+
+class RowidMergeJoinOperation(Operation):
+    """cursor/core/rowid_merge_join.h:29-41: every left row joined with the right row whose number is the left key; a key that is
+    no row of the right table fails the run with ERROR_FOREIGN_KEY_INVALID.  The right side must be ScanView(table); the gather
+    is fused into the left pipeline."""
+
+    def __init__(self, left_key_selector, result_projector, left, right):
+        self.left_key, self.result_projector = left_key_selector, result_projector
+        self.child, self.rhs_child = left, right
+
+    def _emit(self, b):
+        c = self.child._emit(b)
+        r = _emit_aux_side(b, self.rhs_child, "RowidMergeJoin")
+        pf, pn = b.proj(self.left_key)
+        p3f, p3n = b.proj(self.result_projector)
+        return b.op(kind=L.OP_ROWID_MERGE_JOIN, child=c, child2=r, proj_first=pf, proj_n=pn, proj3_first=p3f, proj3_n=p3n)
+
+
+def RowidMergeJoin(left_key_selector, result_projector, left, right):
+    return RowidMergeJoinOperation(left_key_selector, result_projector, left, right)
+
+
 def _array(ctype, items):
     arr = (ctype * max(len(items), 1))()
     for i, it in enumerate(items):
@@ -1524,7 +1582,7 @@ class Plan(object):
         """Chunked staging (ssgpu_plan_run_host): the HOST columns of `view` (default: the plan's input) travel through two alternating
         sets of device columns of chunk_rows rows, chunk k + 1 being copied while chunk k is read -- inputs larger than device
         memory run, and the copy overlaps the kernels (pinned numpy memory, e.g. torch's pin_memory, for the copies to be
-        asynchronous).  ScalarAggregate plans, row-local plans (Filter / Compute / Project / HashJoin) and plans whose first blocking
+        asynchronous).  ScalarAggregate plans, row-local plans (Filter / Compute / Project / HashJoin / ForeignFilter / RowidMergeJoin) and plans whose first blocking
         operation is a GroupAggregate of mergeable aggregates (include/ssgpu.h, "CHUNKED STAGING"); NOT_IMPLEMENTED otherwise."""
         view = view if view is not None else self.input
         if isinstance(view, DeviceView):

@@ -123,6 +123,24 @@ Status bind_projector(const PlanDesc& d, int first, int n, const Schema& schema,
   return Status::OK();
 }
 
+// The key of a ForeignFilter / RowidMergeJoin (EnsureSingleColumnRowidTypeNotNull, foreign_filter.cc:188-213 and
+// rowid_merge_join.cc:186-211): the selector binds to exactly one attribute, of the row-id type INT64, that is not nullable.
+Status bind_rowid_key(const PlanDesc& d, int first, int n, const Schema& schema, int* position) {
+  std::vector<int> pos; std::vector<std::string> names;
+  SS_RETURN_IF_ERROR(bind_projector(d, first, n, schema, &pos, &names));
+  if (pos.size() != 1)
+    return Status::Error(SSGPU_ERROR_ATTRIBUTE_COUNT_MISMATCH, "Expected exactly 1 attribute for the key; found: " + std::to_string(pos.size()));
+  const Attr& a = schema[pos[0]];
+  if (a.dtype != SSGPU_INT64)
+    return Status::Error(SSGPU_ERROR_ATTRIBUTE_TYPE_MISMATCH,
+                         "Column " + names[0] + " designated as a key has type " + dtype_name(a.dtype) + "; expected INT64");
+  if (a.nullable)
+    return Status::Error(SSGPU_ERROR_ATTRIBUTE_IS_NULLABLE,
+                         "Column " + names[0] + " designated as a key is nullable. Please remove nullability explicitly (by casting, or using NVL)");
+  *position = pos[0];
+  return Status::OK();
+}
+
 // ---- constants -------------------------------------------------------------------
 static uint64_t const_bits(int dtype, int64_t i64, double f64) {
   uint64_t b = 0;

@@ -61,13 +61,14 @@ std::string schema_to_string(const Schema& s);
 struct BExpr;
 typedef std::shared_ptr<BExpr> BExprP;
 struct BExpr {
-  enum Kind { INPUT, CONST, NULLCONST, OP, CAST, JOINCOL, JOINMATCH, JOINSTART, JOINCNT, ROWID /* the row's index in the plan's input (UINT64) */ } kind = INPUT;
+  enum Kind { INPUT, CONST, NULLCONST, OP, CAST, JOINCOL, JOINMATCH, JOINSTART, JOINCNT, ROWID /* the row's index in the plan's input (UINT64) */,
+              JOINROW /* the matched row of the join's rhs table itself (UINT32; VM_NONE without a match): ForeignFilter's new key */ } kind = INPUT;
   int op = 0;          // reference OperatorId for OP
   int dtype = SSGPU_INT64;
   bool nullable = false;
   std::string name;
   int input_col = -1;  // INPUT: column of the stage input; JOINCOL: column of the join's rhs table
-  int join_id = -1;    // JOINCOL / JOINMATCH / JOINSTART / JOINCNT: index into the stage's joins
+  int join_id = -1;    // JOINCOL / JOINMATCH / JOINSTART / JOINCNT / JOINROW: index into the stage's joins
   uint64_t bits = 0;   // CONST: raw value bits in the column's device width
   int filter_depth = 0;  // number of Filter operations below this expression
   // string-producing OP (OP_LTRIM ... OP_SUBSTRING; args = the STRING argument alone): SUBSTRING's constant position and length
@@ -106,7 +107,13 @@ struct SortKey { int col; int order; };
 // HashJoin fused into a pipeline (hash_join.h:37-56, UNIQUE rhs keys): lhs key expressions are
 // packed like group keys, probed against an index built over the rhs table (the plan's auxiliary
 // input) and the referenced rhs columns are gathered by the matched row.
+// The structured-filter joins (foreign_filter.h:25-47, rowid_merge_join.h:29-41) are two more FORMS of the same spec: they answer
+// in the same matched-row register, so the gathers, the match filter and everything that fuses with a UNIQUE INNER HashJoin serve
+// them unchanged, but they build no index -- SEARCH looks the one INT64 key up in the sorted key column of the auxiliary table
+// (rhs_key_cols[0]; the runtime verifies the order), ROWID takes the key as the row (rhs_key_cols and fields are empty).
 struct JoinSpec {
+  enum Form { HASH = 0, SEARCH = 1, ROWID = 2 };
+  int form = HASH;
   int type = 0;                          // SSGPU_JOIN_INNER / SSGPU_JOIN_LEFT_OUTER
   std::vector<BExprP> lhs_keys;          // over the stage input
   std::vector<int> rhs_key_cols;         // columns of the auxiliary input
@@ -311,6 +318,8 @@ Status bind_expression(const PlanDesc& d, int expr_index, const Schema& schema, 
 // projector binding: positions into `schema` + result names
 Status bind_projector(const PlanDesc& d, int first, int n, const Schema& schema,
                       std::vector<int>* positions, std::vector<std::string>* names);
+// the key selector of a ForeignFilter / RowidMergeJoin: exactly one attribute (401), INT64 (402), not nullable (406)
+Status bind_rowid_key(const PlanDesc& d, int first, int n, const Schema& schema, int* position);
 std::string bexpr_to_string(const BExprP& e);
 
 // lower.cpp: operation chain -> stages

@@ -229,6 +229,8 @@ struct JoinBuildParams {
 hipError_t ssgpu_launch_join_expand(const unsigned int* offsets, const unsigned int* run_start, const unsigned int* rows_sorted,
                                     unsigned long long n_lhs, unsigned long long n_out, unsigned int* lhs_idx, unsigned int* rhs_row, hipStream_t stream);
 hipError_t ssgpu_launch_join_build(const JoinBuildParams& P, hipStream_t stream);
+// ForeignFilter: *flag |= 1 unless the n INT64 keys are strictly ascending (signed); *flag is the caller's to clear
+hipError_t ssgpu_launch_keys_ascending(const long long* keys, unsigned long long n, unsigned int* flag, hipStream_t stream);
 hipError_t ssgpu_launch_fill_u32(unsigned int* p, unsigned int v, size_t n, hipStream_t stream);
 // one launch for all a GroupAggregate run clears: keys[n_keys] = EMPTY, acc[i] = pattern[i % ng] (n_acc words), cnt[n_cnt] = 0,
 // z[q][0 .. nz[q]) = 0 (32-bit words; unused: nz = 0)

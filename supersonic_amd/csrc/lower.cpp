@@ -150,7 +150,7 @@ class Emitter {
   bool reads_join(const BExprP& e) {
     auto it = reads_join_.find(e.get());
     if (it != reads_join_.end()) return it->second;
-    bool f = e->kind == BExpr::JOINCOL || e->kind == BExpr::JOINMATCH || e->kind == BExpr::JOINSTART || e->kind == BExpr::JOINCNT;
+    bool f = e->kind == BExpr::JOINCOL || e->kind == BExpr::JOINMATCH || e->kind == BExpr::JOINSTART || e->kind == BExpr::JOINCNT || e->kind == BExpr::JOINROW;
     for (auto& a : e->args) f = f || reads_join(a);
     reads_join_[e.get()] = f;
     return f;
@@ -199,6 +199,7 @@ std::string Emitter::key_of(const BExprP& e) {
     case BExpr::JOINMATCH: s << "M" << e->join_id; break;
     case BExpr::JOINSTART: s << "JS" << e->join_id; break;
     case BExpr::JOINCNT: s << "JC" << e->join_id; break;
+    case BExpr::JOINROW: s << "JR" << e->join_id; break;
     case BExpr::ROWID: s << "R"; break;
     default:
       s << (e->kind == BExpr::CAST ? "K" : "O") << e->op << ":" << e->dtype << ":" << e->filter_depth;
@@ -265,6 +266,19 @@ Status Emitter::join_index(int join_id, int* reg) {
   if (it != join_idx_.end()) { *reg = it->second; return Status::OK(); }
   if (!joins_ || join_id < 0 || join_id >= (int)joins_->size()) return Status::Error(SSGPU_ERROR_UNKNOWN, "join reference outside its stage");
   const JoinSpec& js = (*joins_)[join_id];
+  if (js.form != JoinSpec::HASH) {
+    // ForeignFilter / RowidMergeJoin: the one INT64 NOT NULL key register is searched for, or is, the row.  Only the rows that
+    // passed the Filters below are looked at; nothing is hoisted in front of a ROWID join (emit_filters), whose rows can fail the run.
+    Val v; SS_RETURN_IF_ERROR(value(js.lhs_keys[0], &v));
+    const int keyreg = materialize(v);
+    const int sel = js.depth >= 0 && js.depth < (int)sel_by_depth.size() ? sel_by_depth[js.depth] : -1;
+    const int idx = new_reg(4);
+    LInstr& i = emit(js.form == JoinSpec::SEARCH ? VM_JOIN_SEARCH : VM_JOIN_ROWID);
+    i.dst = idx; i.a = keyreg; i.d = sel; i.imm = (uint64_t)join_id;
+    join_idx_[join_id] = idx;
+    *reg = idx;
+    return Status::OK();
+  }
   // pack the lhs key exactly as the index build packs the rhs key (JoinBuildParams)
   int keyreg = -1, keyreg_hi = -1;
   int any_null = -1;   // a NULL in any key column: the row matches nothing
@@ -399,6 +413,10 @@ Status Emitter::value(const BExprP& e, Val* out) {
       int idx; SS_RETURN_IF_ERROR(join_index(e->join_id, &idx));
       v.reg = new_reg(1);
       LInstr& i = emit(VM_IDX_VALID); i.dst = v.reg; i.a = idx;
+    } break;
+    case BExpr::JOINROW: {   // the matched row itself: the probe's register (never written to: a value may share it)
+      int idx; SS_RETURN_IF_ERROR(join_index(e->join_id, &idx));
+      v.reg = idx;
     } break;
     case BExpr::JOINSTART: case BExpr::JOINCNT: {
       // multi join: the probe yields the key's slot; its run of rhs rows is [start, start + count)
@@ -1070,8 +1088,10 @@ static void reset_pipe(Pipe* p, const Schema& in) {
   }
 }
 
-// emit the filter chain; fills em.sel_by_depth
-static Status emit_filters(Emitter& em, const Pipe& pipe) {
+// emit the filter chain; fills em.sel_by_depth.  `checks`: a RowidMergeJoin is emitted even when nothing reads its columns -- its
+// out-of-range keys fail the run whatever the result projector keeps (the count pass of a materialising stage leaves that to the
+// store pass, which runs whenever it does).
+static Status emit_filters(Emitter& em, const Pipe& pipe, bool checks = true) {
   em.filters_ = &pipe.filters;
   em.hoist_ok_ = !pipe.joins.empty();
   for (auto& f : pipe.filters) em.hoist_ok_ = em.hoist_ok_ && !em.may_fail(f);
@@ -1093,6 +1113,9 @@ static Status emit_filters(Emitter& em, const Pipe& pipe) {
     i.c = em.sel_by_depth.back();
     em.sel_by_depth.push_back(r);
   }
+  if (checks)
+    for (size_t j = 0; j < pipe.joins.size(); ++j)
+      if (pipe.joins[j].form == JoinSpec::ROWID) { int idx; SS_RETURN_IF_ERROR(em.join_index((int)j, &idx)); }
   return Status::OK();
 }
 
@@ -1658,7 +1681,7 @@ static Status finish_materialize(const Pipe& pipe, Stage* st) {
   st->has_filter = !pipe.filters.empty();
   if (st->has_filter) {
     Emitter ec(&st->count_pass, &pipe.joins);
-    SS_RETURN_IF_ERROR(emit_filters(ec, pipe));
+    SS_RETURN_IF_ERROR(emit_filters(ec, pipe, false));
     LInstr& i = ec.emit(VM_SEL_COUNT); i.dst_is_reg = false; i.dst = 0; i.a = ec.sel_by_depth.back();
     allocate_registers(&st->count_pass);
   }
@@ -1966,6 +1989,69 @@ Status lower_plan(const PlanDesc& d, std::vector<Stage>* stages, Schema* result_
         pipe.joins.push_back(js);
         pipe.cols = nc; pending = true;
         desc << (jtype == SSGPU_JOIN_INNER ? "HashJoin INNER" : "HashJoin LEFT_OUTER") << " -> [" << schema_to_string(schema_of(pipe.cols)) << "]\n";
+      } break;
+      case SSGPU_OP_FOREIGN_FILTER: case SSGPU_OP_ROWID_MERGE_JOIN: {
+        // The structured-filter joins (foreign_filter.h:25-47, rowid_merge_join.h:29-41) as join forms of this pipeline: one more
+        // JoinSpec, no stage of their own -- the Filters below and whatever follows share the kernel, as with a UNIQUE INNER HashJoin.
+        const bool ff = op.kind == SSGPU_OP_FOREIGN_FILTER;
+        const char* opname = ff ? "ForeignFilter" : "RowidMergeJoin";
+        if (op.child2 < 0 || op.child2 >= (int)d.ops.size() || d.ops[op.child2].kind != SSGPU_OP_SCAN || d.ops[op.child2].option0 != 1)
+          return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, std::string("the ") + (ff ? "filter" : "right") + " side of a device " + opname +
+                                                                " must be a scan of the auxiliary input (a resident table)");
+        if ((int)pipe.joins.size() >= VM_MAX_JOINS)
+          return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "too many joins in one pipeline");
+        const Schema& rs = d.aux_schema;
+        JoinSpec js; js.form = ff ? JoinSpec::SEARCH : JoinSpec::ROWID; js.type = SSGPU_JOIN_INNER; js.depth = pipe.depth();
+        int kpos = -1;
+        if (ff) {   // the filter's key first, then the input's (foreign_filter.cc:230-239)
+          int fpos = -1;
+          SS_RETURN_IF_ERROR(bind_rowid_key(d, op.proj2_first, op.proj2_n, rs, &fpos));
+          js.rhs_key_cols.push_back(fpos);
+        }
+        SS_RETURN_IF_ERROR(bind_rowid_key(d, op.proj_first, op.proj_n, vs, &kpos));
+        js.lhs_keys.push_back(pipe.cols[kpos].expr);
+        const int join_id = (int)pipe.joins.size();
+        auto join_expr = [&](BExpr::Kind k, int dtype, const std::string& name) {
+          BExprP e(new BExpr);
+          e->kind = k; e->join_id = join_id; e->dtype = dtype; e->nullable = false; e->name = name; e->filter_depth = pipe.depth();
+          return e;
+        };
+        std::vector<VCol> nc;
+        if (ff) {
+          // the input's schema in the input's order; the key column keeps its name and becomes the filter row that holds the key,
+          // widened to INT64 (BoundForeignFilter, foreign_filter.cc:262-291); rows without one are dropped like an inner join's
+          nc = pipe.cols;
+          BExprP key(new BExpr);
+          key->kind = BExpr::CAST; key->dtype = SSGPU_INT64; key->nullable = false; key->name = nc[kpos].name; key->filter_depth = pipe.depth();
+          key->args.push_back(join_expr(BExpr::JOINROW, SSGPU_UINT32, "FILTER_ROW"));
+          nc[kpos].expr = key;
+          pipe.filters.push_back(join_expr(BExpr::JOINMATCH, SSGPU_BOOL, "JOIN_MATCH"));
+        } else {
+          // the result projector, bound as a HashJoin's; every selected left row keeps its place: a key outside the right table
+          // fails the run (VM_JOIN_ROWID), so there is no match filter and no NULL extension
+          for (int q = 0; q < op.proj3_n; ++q) {
+            const ssgpu_proj& pr = d.projs[op.proj3_first + q];
+            if (pr.source != 0 && pr.source != 1) return Status::Error(SSGPU_ERROR_INVALID_ARGUMENT_VALUE, "RowidMergeJoin result projector: source index must be 0 or 1");
+            std::vector<int> pos; std::vector<std::string> names;
+            SS_RETURN_IF_ERROR(bind_projector(d, op.proj3_first + q, 1, pr.source == 0 ? vs : rs, &pos, &names));
+            for (size_t i = 0; i < pos.size(); ++i) {
+              VCol c;
+              if (pr.source == 0) c = pipe.cols[pos[i]];
+              else {
+                BExprP e = join_expr(BExpr::JOINCOL, rs[pos[i]].dtype, names[i]);
+                e->input_col = pos[i]; e->nullable = rs[pos[i]].nullable;
+                if (dtype_width(e->dtype) == 0) return Status::Error(SSGPU_ERROR_NOT_IMPLEMENTED, "right column type is outside the device hot path");
+                c.expr = e;
+              }
+              c.name = names[i];
+              for (auto& o : nc) if (o.name == c.name) return Status::Error(SSGPU_ERROR_ATTRIBUTE_EXISTS, "Duplicate attribute name \"" + c.name + "\" in result schema");
+              nc.push_back(c);
+            }
+          }
+        }
+        pipe.joins.push_back(js);
+        pipe.cols = nc; pending = true;
+        desc << opname << " -> [" << schema_to_string(schema_of(pipe.cols)) << "]\n";
       } break;
       case SSGPU_OP_SCALAR_AGGREGATE: case SSGPU_OP_GROUP_AGGREGATE: case SSGPU_OP_BEST_EFFORT_GROUP_AGGREGATE: {
         // BestEffortGroupAggregate (aggregate.h:230-250, aggregate_groups.cc:332-433): a GroupAggregate whose table holds a bounded

@@ -1976,6 +1976,17 @@ hipError_t ssgpu_launch_join_build(const JoinBuildParams& P, hipStream_t stream)
   if (P.n_rows) hipLaunchKernelGGL(ssgpu_join_build_kernel, dim3((unsigned)((P.n_rows + 255) / 256)), dim3(256), 0, stream, P);
   return hipGetLastError();
 }
+// ForeignFilter: the filter table's keys must be strictly ascending as signed 64-bit values -- what VM_JOIN_SEARCH's lower bound
+// assumes.  Every thread compares one row with its predecessor; *flag is raised (never cleared) where keys[i - 1] >= keys[i].
+__global__ __launch_bounds__(256) void ssgpu_keys_ascending_kernel(const i64* __restrict__ keys, u64 n, u32* __restrict__ flag) {
+  const u64 i = (u64)blockIdx.x * 256 + threadIdx.x + 1;
+  if (i < n && !(keys[i - 1] < keys[i])) atomicOr(flag, 1u);
+}
+hipError_t ssgpu_launch_keys_ascending(const long long* keys, unsigned long long n, unsigned int* flag, hipStream_t stream) {
+  if (n > 1) hipLaunchKernelGGL(ssgpu_keys_ascending_kernel, dim3((unsigned)((n - 1 + 255) / 256)), dim3(256), 0, stream,
+                                reinterpret_cast<const i64*>(keys), (u64)n, flag);
+  return hipGetLastError();
+}
 // GroupAggregate FIRST / LAST: the group's accumulator holds the smallest / largest contributing
 // row id; the result is the input column's value at that row.
 // Value kinds: 0 i32, 1 u32, 2 i64, 3 u64, 4 f32, 5 f64, 6 one byte.  When the result type differs from the column's

@@ -1020,6 +1020,30 @@ int build_joins(ssgpu_plan* p, Stage& st, StageExec& ex) {
   ex.jkeys.resize(nj); ex.jkeys_hi.resize(nj); ex.jrows.resize(nj); ex.jmisc.resize(nj); ex.vm_joins.resize(nj);
   for (size_t j = 0; j < nj; ++j) {
     const JoinSpec& js = st.joins[j];
+    if (js.form != JoinSpec::HASH) {
+      // ForeignFilter / RowidMergeJoin: no index and no allocation beyond the flag word.  The slot carries the auxiliary table's row
+      // count and, for the search, its key column as it lies -- whose order is verified here, where a HashJoin builds its index: one
+      // adjacent-compare launch per run, since the table bound now need not be the one an earlier run saw.
+      VmJoin& J = ex.vm_joins[j];
+      memset(&J, 0, sizeof(J));
+      J.capacity_mask = (uint32_t)p->aux_rows;      // (< VM_NONE: ssgpu_plan_set_aux_input)
+      if (js.form == JoinSpec::SEARCH) {
+        const long long* keys = static_cast<const long long*>(p->aux_cols[js.rhs_key_cols[0]].data);
+        if (p->aux_rows > 0 && !keys) { c->err = "ForeignFilter: the filter's key column has no data"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+        J.keys = reinterpret_cast<const unsigned long long*>(keys);
+        if (p->aux_rows > 1) {
+          HIP_TRY(c, ex.jmisc[j].ensure(16));
+          HIP_TRY(c, hipMemsetAsync(ex.jmisc[j].p, 0, 16, c->stream));
+          HIP_TRY(c, ssgpu_launch_keys_ascending(keys, (unsigned long long)p->aux_rows, ex.jmisc[j].as<unsigned int>(), c->stream));
+          uint32_t unordered = 0;
+          HIP_TRY(c, hipMemcpyAsync(&unordered, ex.jmisc[j].p, 4, hipMemcpyDeviceToHost, c->stream));
+          HIP_TRY(c, hipStreamSynchronize(c->stream));
+          p->counters.n_launches += 1;
+          if (unordered) { c->err = "ForeignFilter: the filter keys must be unique and ascending (a key is not greater than the one before it)"; return SSGPU_ERROR_INVALID_ARGUMENT_VALUE; }
+        }
+      }
+      continue;
+    }
     uint64_t cap = 16; while (cap < (uint64_t)std::max<int64_t>(p->aux_rows, 1) * 2) cap <<= 1;
     if (cap > (1ull << 31)) { c->err = "hash join rhs table too large"; return SSGPU_ERROR_MEMORY_EXCEEDED; }
     HIP_TRY(c, ex.jmisc[j].ensure(16));
@@ -2817,6 +2841,10 @@ int check_error_flags(ssgpu_plan* p) {
   }
   for (uint32_t f : flags) {
     if (f == 3) { c->err = "decoupled look-back: a tile waited for an earlier tile's row count for too long and gave up"; return SSGPU_ERROR_HIP; }
+    if (f == SSGPU_EVAL_ERROR_FOREIGN_KEY) {   // VM_JOIN_ROWID: the message of rowid_merge_join.cc:99-102, the right table's row count in it
+      c->err = "No parent record with ID > " + std::to_string(std::max<int64_t>(p->aux_rows, 0));
+      return SSGPU_ERROR_FOREIGN_KEY_INVALID;
+    }
     if (f) {
       c->err = f == 2 ? "Evaluation error: invalid argument of a signaling math expression (negative input of SQRT)"
                       : "Evaluation error: division by zero in a signaling expression";
@@ -3315,6 +3343,8 @@ static int lookup_name(const Schema& s, const char* name) {
   for (size_t i = 0; i < s.size(); ++i) if (s[i].name == (name ? name : "")) return (int)i;
   return -1;
 }
+// the row-local operations whose `child2` is a scan of the auxiliary input
+static bool op_has_aux_side(int kind) { return kind == SSGPU_OP_HASH_JOIN || kind == SSGPU_OP_FOREIGN_FILTER || kind == SSGPU_OP_ROWID_MERGE_JOIN; }
 // kind 3: the derived plans.  iB = the GroupAggregate in p->desc.ops
 static int stream_job_build_group(ssgpu_plan* p, int iB, ssgpu_plan** head_out, ssgpu_plan** tail_out) {
   ssgpu_ctx* c = p->ctx; const PlanDesc& D = p->desc;
@@ -3455,7 +3485,7 @@ static int stream_job_build_group(ssgpu_plan* p, int iB, ssgpu_plan** head_out, 
       if (r.kind == SSGPU_OP_SCAN && r.option0 == 1) { tops.push_back(r); tail_has_aux = true; remap[(size_t)k] = (int32_t)tops.size() - 1; return remap[(size_t)k]; }
       return -2;
     };
-    o.child = ref(o.child); if (o.kind == SSGPU_OP_HASH_JOIN) o.child2 = ref(o.child2);
+    o.child = ref(o.child); if (op_has_aux_side(o.kind)) o.child2 = ref(o.child2);
     if (o.child == -2 || o.child2 == -2) { ssgpu_plan_destroy(head); c->err = "chunked execution: the operations above the GroupAggregate read more than its result"; return SSGPU_ERROR_NOT_IMPLEMENTED; }
     tops.push_back(o); remap[j] = (int32_t)tops.size() - 1;
   }
@@ -3497,13 +3527,13 @@ static int stream_job_prepare(ssgpu_plan* p, int* kind_out, bool for_run = true)
       for (int i = (int)p->desc.ops.size() - 1; i >= 0; i = p->desc.ops[(size_t)i].child) path.push_back(i);
       for (size_t k = path.size(); k-- > 0;) {
         const ssgpu_op& o = p->desc.ops[(size_t)path[k]];
-        if (o.kind == SSGPU_OP_SCAN || o.kind == SSGPU_OP_COMPUTE || o.kind == SSGPU_OP_FILTER || o.kind == SSGPU_OP_PROJECT || o.kind == SSGPU_OP_HASH_JOIN) continue;
+        if (o.kind == SSGPU_OP_SCAN || o.kind == SSGPU_OP_COMPUTE || o.kind == SSGPU_OP_FILTER || o.kind == SSGPU_OP_PROJECT || op_has_aux_side(o.kind)) continue;
         if (o.kind == SSGPU_OP_GROUP_AGGREGATE && o.option0 == 0) { kind = 3; iB = path[k]; }
         break;
       }
     }
     if (!kind) {
-      c->err = "chunked staging serves plans of row-local operations (Filter / Compute / Project / HashJoin), ScalarAggregates over them, and plans whose "
+      c->err = "chunked staging serves plans of row-local operations (Filter / Compute / Project / HashJoin / ForeignFilter / RowidMergeJoin), ScalarAggregates over them, and plans whose "
                "first blocking operation is a GroupAggregate without a key limit; other plans take device columns (ssgpu_block_upload + ssgpu_plan_run_block)";
       return SSGPU_ERROR_NOT_IMPLEMENTED;
     }

@@ -122,7 +122,7 @@ enum { VM_MATH_EXP = 1, VM_MATH_LN, VM_MATH_LOG10, VM_MATH_LOG2, VM_MATH_SIN, VM
   X(AGG_SUM_F64_ADD) X(AGG_SUM_F64_SUB) X(AGG_SUM_F64_MUL)                     \
   /* ---- materialising sinks ---------------------------------------------- */\
   X(SEL_COUNT)   /* a = sel: tile_counts[tile] = #selected        */           \
-  X(SEL_RANK) X(PART_RANK) X(PART_REC_8) X(PART_REC_32) X(PART_REC_64) X(PART_REC_128) X(PART_FLUSH) X(JOIN_PROBE) X(JOIN_PROBE_WIDE) X(IDX_VALID) X(GATHER_64) X(GATHER_32) X(GATHER_8) X(GATHER_NULL)    /* a = sel, dst = u32 rank reg (absolute out row) */          \
+  X(SEL_RANK) X(PART_RANK) X(PART_REC_8) X(PART_REC_32) X(PART_REC_64) X(PART_REC_128) X(PART_FLUSH) X(JOIN_PROBE) X(JOIN_PROBE_WIDE) X(JOIN_SEARCH) X(JOIN_ROWID) X(IDX_VALID) X(GATHER_64) X(GATHER_32) X(GATHER_8) X(GATHER_NULL)    /* a = sel, dst = u32 rank reg (absolute out row) */          \
   X(STORE_8) X(STORE_32) X(STORE_64)     /* dst = out col, a = reg, rows 1:1 */\
   X(STOREC_8) X(STOREC_32) X(STOREC_64)  /* + b = rank reg, c = sel (compact)*/\
   X(STORE_ROWID) /* dst = out col: int64 global row id of survivors, b,c */    \
@@ -219,13 +219,21 @@ struct VmGroupTable {
  * row (or VM_NONE) in a u32 register; GATHER_* (imm = slot of join_cols) fetch rhs values by it. */
 struct VmJoin {
   const unsigned long long* keys;   /* JOIN_PROBE: capacity {key, answer} pairs (16 bytes each), key == VM_KEY_EMPTY = free;
-                                       JOIN_PROBE_WIDE: the first key word of every entry */
+                                       JOIN_PROBE_WIDE: the first key word of every entry;
+                                       JOIN_SEARCH: the filter table's key column itself -- INT64, strictly ascending */
   const unsigned int* rows;         /* JOIN_PROBE_WIDE: rhs row of every entry, VM_NONE = free */
   const unsigned int* special;      /* [0]: rhs row whose packed key equals VM_KEY_EMPTY, or VM_NONE */
-  uint32_t capacity_mask;
+  uint32_t capacity_mask;           /* JOIN_SEARCH / JOIN_ROWID: the auxiliary table's ROW COUNT (< VM_NONE), no mask */
   uint32_t answer_slot;             /* JOIN_PROBE_WIDE: 1 = answer with the key's slot (NOT_UNIQUE index), 0 = with rows[slot] */
   const unsigned long long* keys_hi; /* JOIN_PROBE_WIDE: second word of every entry's key (rows[slot] == VM_NONE = free) */
 };
+/* The structured-filter joins take the same slot and answer in the same u32 row register, without an index:
+ * JOIN_SEARCH (ForeignFilter): a = INT64 key register, d = selection, imm = join number.  dst = the row j of the auxiliary table with
+ *   keys[j] == key, VM_NONE when there is none (or the row is not selected): a lower bound over the sorted column whose steps
+ *   depend on the row count alone -- every lane of a wave walks the same number of levels, signed compares, a count of 0 loads nothing.
+ * JOIN_ROWID (RowidMergeJoin): a = INT64 key register, d = selection.  dst = (u32)key where 0 <= key < row count, compared as the
+ *   signed 64-bit value before narrowing; a selected row of the input outside that range raises SSGPU_EVAL_ERROR_FOREIGN_KEY in the
+ *   error word and gets VM_NONE, so the gathers behind it stay inside the table in a failing run too. */
 struct VmJoinCol { const void* data; const unsigned char* is_null; };
 #define VM_MAX_JOINS 2
 #define VM_MAX_JOIN_COLS 24
@@ -283,6 +291,10 @@ static inline const char* vm_op_name(uint16_t op) {
   return op < VM_OP_COUNT_ ? names[op] : "?";
 }
 #endif
+
+/* Low byte of a stage's error word (evaluation errors, check_error_flags in runtime.cpp): 1 = division by zero (SSGPU_EVAL_ERROR_DIVZERO,
+ * vm_body.inc), 2 = invalid argument of a signaling math expression, 3 = a look-back gave up, and */
+#define SSGPU_EVAL_ERROR_FOREIGN_KEY 4u   /* JOIN_ROWID: a selected row's key is no row of the right table (ERROR_FOREIGN_KEY_INVALID) */
 
 /* Bit of a stage's error word: a NaN reached a floating MIN / MAX.  The kernels skip NaNs (order-independent); the reference keeps
  * a NaN that is the group's FIRST non-NULL value (aggregation_operators.h:189-228), so the host repeats such a run with the

@@ -482,6 +482,53 @@
             lds_store2<u32>(I.dst, p, r[0], r[1]);
           }
         } break;
+        // ---- the structured-filter joins: no index, the same u32 row register (see VmJoin in vm.h) ----
+        case VM_JOIN_SEARCH: { CASE_FENCE;   // ForeignFilter: the row of the sorted filter column that holds the key, or VM_NONE
+          // A lower bound whose trip count depends on the table's row count alone: every lane walks the same levels and only
+          // its base moves (a select, no branch), so a wave never diverges; the upper levels are a handful of lines that every
+          // row of every tile reads again and stay in the caches (L2 / Infinity Cache), the last levels are the gather.  The two
+          // rows of a pair are two independent chains in flight.  Invariant: base + len <= n, so keys[base + half - 1] is a row of
+          // the table whatever the key is -- rows that are not selected (and the tile's tail, whose registers hold anything)
+          // search for INT64 min, stay at base 0 and read what the wave's other lanes read anyway.
+          const VmJoin J = P.join[I.imm & (VM_MAX_JOINS - 1)];
+          const i64* __restrict__ keys = reinterpret_cast<const i64*>(J.keys);
+          const u32 n = J.capacity_mask;
+          _Pragma("unroll 1") FOR_PAIRS {    // (pair after pair: more chains per lane only add registers to a kernel that has none to spare)
+            auto kk = lds_load2<u64>(I.a, p);
+            Valid2 m = valid_pair_(p, tile_valid, VM_NONE, I.d);
+            const i64 lowest = (i64)0x8000000000000000ull;
+            const i64 k0 = m.x ? (i64)kk.x : lowest, k1 = m.y ? (i64)kk.y : lowest;
+            u32 b0 = 0, b1 = 0;
+            for (u32 len = n; len > 1;) {
+              const u32 half = len >> 1;
+              const i64 e0 = keys[b0 + half - 1], e1 = keys[b1 + half - 1];
+              b0 = e0 < k0 ? b0 + half : b0;
+              b1 = e1 < k1 ? b1 + half : b1;
+              len -= half;
+            }
+            u32 r0 = VM_NONE, r1 = VM_NONE;
+            if (n != 0) {                    // (uniform: an empty table has no keys[0])
+              const i64 f0 = keys[b0], f1 = keys[b1];
+              r0 = (m.x && f0 == k0) ? b0 : VM_NONE;
+              r1 = (m.y && f1 == k1) ? b1 : VM_NONE;
+            }
+            lds_store2<u32>(I.dst, p, r0, r1);
+          }
+        } break;
+        case VM_JOIN_ROWID: { CASE_FENCE;    // RowidMergeJoin: the key IS the right row; outside [0, n) a selected row fails the run
+          const VmJoin J = P.join[I.imm & (VM_MAX_JOINS - 1)];
+          const i64 n = (i64)J.capacity_mask;
+          bool bad = false;
+          _Pragma("unroll") FOR_PAIRS {
+            auto kk = lds_load2<u64>(I.a, p);
+            Valid2 m = valid_pair_(p, tile_valid, VM_NONE, I.d);
+            const i64 k0 = (i64)kk.x, k1 = (i64)kk.y;          // compared as signed 64-bit values BEFORE the narrowing
+            const bool in0 = k0 >= 0 && k0 < n, in1 = k1 >= 0 && k1 < n;
+            bad = bad || (m.x && !in0) || (m.y && !in1);
+            lds_store2<u32>(I.dst, p, (m.x && in0) ? (u32)k0 : VM_NONE, (m.y && in1) ? (u32)k1 : VM_NONE);
+          }
+          if (bad) atomicExch(P.error_flag, (u32)SSGPU_EVAL_ERROR_FOREIGN_KEY);
+        } break;
         case VM_ROWID_64: { CASE_FENCE;      // global row id of every row of the tile
           _Pragma("unroll") FOR_PAIRS {
             const u64 r0 = (u64)(P.row_id_base + tile_base + 2 * (i64)p);
