@@ -220,6 +220,7 @@ __global__ __launch_bounds__(256) void ssgpu_dense_fold_kernel(const DenseFoldPa
       const u64* a = reinterpret_cast<const u64*>(static_cast<const char*>(P.chunks) + (u64)c * P.chunk_bytes + acc_off);
       const double bh = u2d_x(a[i]), bl = u2d_x(a[i + 1]);
       const double s = hi + bh, bb = s - hi;
+      if (!__builtin_isfinite(s)) { hi = s; lo = 0.0; continue; }   // a non-finite sum wins: TwoSum's error term of it is NaN (emit_value)
       double e = (hi - (s - bb)) + (bh - bb);     // TwoSum: s + e == hi + bh exactly
       e += lo + bl;
       const double h2 = s + e;

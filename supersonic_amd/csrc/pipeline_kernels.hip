@@ -933,7 +933,7 @@ __device__ __forceinline__ VmAccRec state_to_slot(const u64* __restrict__ state,
     case SLOT_SUM_DD: {
       // the ranks' hi and lo parts were summed independently; renormalise
       DD a; a.hi = u2d(state[2 * n_slots + s]); a.lo = 0.0;
-      a = dd_add_d(a, u2d(state[3 * n_slots + s]));
+      if (__builtin_isfinite(a.hi)) a = dd_add_d(a, u2d(state[3 * n_slots + s]));   // (a non-finite hi wins: emit_value)
       r.v0 = d2u(a.hi); r.v1 = d2u(a.lo);
     } break;
     case SLOT_MIN_U64: r.v0 = state[4 * n_slots + s] ^ 0x8000000000000000ull; break;
@@ -999,12 +999,14 @@ __device__ __forceinline__ void emit_value(void* dst, size_t idx, int out_kind, 
     case EMIT_I32KEY: reinterpret_cast<i32*>(dst)[idx] = (i32)unkey_i64(v0); break;
     case EMIT_F64: reinterpret_cast<double*>(dst)[idx] = u2d(v0); break;
     case EMIT_F32: reinterpret_cast<float*>(dst)[idx] = (float)u2d(v0); break;
+    // a non-finite hi wins: it was folded by plain IEEE adds, so it has the class (+-inf / NaN) of the reference's row-after-row sum,
+    // while TwoSum's error term of a non-finite add is NaN (inf - inf) and would poison hi + lo; its residual is 0
     case EMIT_DD_F64: { double hi = u2d(v0), lo = u2d(v1);
-      reinterpret_cast<double*>(dst)[idx] = (lo == 0.0) ? hi : hi + lo; } break;
+      reinterpret_cast<double*>(dst)[idx] = (lo == 0.0 || !__builtin_isfinite(hi)) ? hi : hi + lo; } break;
     case EMIT_DDRES_F64: { const double hi = u2d(v0), lo = u2d(v1), sm = hi + lo, bp = sm - hi;   // TwoSum: exact
-      reinterpret_cast<double*>(dst)[idx] = (lo == 0.0) ? 0.0 : (hi - (sm - bp)) + (lo - bp); } break;
+      reinterpret_cast<double*>(dst)[idx] = (lo == 0.0 || !__builtin_isfinite(hi)) ? 0.0 : (hi - (sm - bp)) + (lo - bp); } break;
     case EMIT_DD_F32: { double hi = u2d(v0), lo = u2d(v1);
-      reinterpret_cast<float*>(dst)[idx] = (float)((lo == 0.0) ? hi : hi + lo); } break;
+      reinterpret_cast<float*>(dst)[idx] = (float)((lo == 0.0 || !__builtin_isfinite(hi)) ? hi : hi + lo); } break;
     case EMIT_U8: reinterpret_cast<u8*>(dst)[idx] = (u8)(v0 != 0); break;
     default: break;
   }

@@ -828,7 +828,8 @@ __global__ void ssgpu_dense_extract_kernel(const DenseExtractParams P) {
     if (o.out_kind == EMIT_DD_F64 || o.out_kind == EMIT_DDRES_F64) {   // compensated DOUBLE sum: (sum, compensation) in consecutive words
       const double hi = __longlong_as_double((i64)P.acc[i * P.n_gaggs + o.s]), lo = __longlong_as_double((i64)P.acc[i * P.n_gaggs + o.s + 1]);
       const double sm = hi + lo, bp = sm - hi;
-      reinterpret_cast<double*>(o.data)[i] = o.out_kind == EMIT_DD_F64 ? (lo == 0.0 ? hi : sm) : (lo == 0.0 ? 0.0 : (hi - (sm - bp)) + (lo - bp));   // the sum / its exact residual (TwoSum)
+      const bool plain = lo == 0.0 || !__builtin_isfinite(hi);   // a non-finite hi wins, its residual is 0 (emit_value in pipeline_kernels.hip)
+      reinterpret_cast<double*>(o.data)[i] = o.out_kind == EMIT_DD_F64 ? (plain ? hi : sm) : (plain ? 0.0 : (hi - (sm - bp)) + (lo - bp));   // the sum / its exact residual (TwoSum)
     } else dense_emit(o.data, i, o.out_kind, P.acc[i * P.n_gaggs + o.s]);
     if (o.is_null) o.is_null[i] = o.has_cnt ? (P.cnt[i * P.n_gaggs + o.s] == 0) : 0;
   }
